@@ -1,6 +1,21 @@
 """Benchmark: rate-limit decisions/sec of the MI355X fixed-window backend.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and no more: it sets up (table,
+fill, input batches), warms up, times the K steps, writes the last timed
+step's outputs if --dump-outputs is given, and prints the result line (value,
+ms_per_step, and the roofline figures sampled inside the timed steps). --full
+adds every other measurement and check, each outside the timed region: batch
+latency one at a time and under load, the host-fed (PCIe) rates, the self-check
+against the C oracle and the CPU baseline (their own options, --latency-steps
+and the like, size or switch them off under --full and mean nothing without it).
+
+--dump-outputs DIR writes the arrays the caller of the last timed step received
+(code, limit_remaining, reset_s, stats) as DIR/<name>.npy in float64 (rank r > 0:
+DIR/<name>.rank<r>.npy). The input batches and clocks are seeded, so two builds
+run with the same arguments are comparable output for output (the stem-hash key
+is drawn per run unless --hash-seed is given; the answers do not depend on it).
 
 A step is one DoLimit batch over device-resident packed input (BASELINE.json
 configs[1] = C1 by default: 10M tenant stems x {sec, min} per GPU, 500k
@@ -19,7 +34,7 @@ Besides the contract line, rank 0 reports:
   roofline      dominant kernel (k_table) achieved GB/s on the canonical
                 B_alg = key_len + 16 + 12 + 64 B per decision,
                 from HIP events on the library's stream;
-  cpu_baseline  the C restatement oracle, key-sharded over the host's cores
+  cpu_baseline  (--full) the C restatement oracle, key-sharded over the host's cores
                 (and on 1 core), on a bounded sample of the same stream.
 """
 import argparse
@@ -86,7 +101,19 @@ def parse():
     ap.add_argument("--loopback", type=int, default=0,
                     help="W > 0: W ranks of the library router as threads of this process, all on cuda:0, "
                          "exchanging through the in-process loopback transport (the W-rank protocol on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: batch latency (one at a "
+                         "time and under load), the host-fed (PCIe) rates, the self-check against the C oracle and "
+                         "the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (code, limit_remaining, "
+                         "reset_s, stats) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.latency_steps = args.loaded_steps = args.pcie_steps = 0
+        args.no_cpu_baseline = True
+    if args.dump_outputs and args.loopback:
+        ap.error("--dump-outputs is not available with --loopback")
     if not args.tenants:
         args.tenants = 62_500_000 if args.config == "c3" else 10_000_000
     if not args.slots_per_key:  # c3: 2^28 x 64-B slots (17 GB) + 2^26 ring lines (8.6 GB) per GPU
@@ -305,11 +332,14 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     barrier()
-    # (after the timed region) the last timed batch's answers, checked below against the oracle
+    # (after the timed region) the last timed batch's answers: written out for
+    # --dump-outputs, checked below against the oracle under --full
     last_out = {k: v.cpu().numpy().view(np.uint32) if v.dtype == torch.int32 else v.cpu().numpy()
                 for k, v in out_chk.items()}
     last_step = check_step
     assert step[0] - 1 == check_step
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out, rank)
     route_host = {k: round(v / args.steps * 1e3, 4) for k, v in sc.host_s.items()} if py_route else None
     info1 = be.table_info()
     if routed and not recv:  # decisions this rank's table answered per owner batch
@@ -356,18 +386,20 @@ def main():
     # whole history (fill, warmup, timed steps, every rank's slices in global
     # order); keys are independent, so the subset's answers must be equal.
     # A wrong-answer fast path cannot post a line.
-    check = verify(args, W, last_out, last_step, host_batches[0][1], world, rank, T, now0, sampler)
-    if routed:
+    check = verify(args, W, last_out, last_step, host_batches[0][1], world, rank, T, now0, sampler) if args.full \
+        else None
+    if check and routed:
         ok = torch.tensor([1 if check["verified"] else 0], dtype=torch.int32,
                           device="cuda" if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         check["verified"] = check["verified"] and bool(ok.item())
-    if not check["verified"]:
+    if check and not check["verified"]:
         print("[bench] SELF-CHECK FAILED (rank %d): %s; no result line (unverified rate %.4g decisions/s, %.4f ms "
               "per step)" % (rank, json.dumps(check), value, elapsed / args.steps * 1e3), file=sys.stderr, flush=True)
         be.close()
         raise SystemExit(1)
-    progress("self-check: %d descriptors equal to the oracle" % check["checked"])
+    if check:
+        progress("self-check: %d descriptors equal to the oracle" % check["checked"])
 
     if rank != 0:
         be.close()
@@ -450,19 +482,29 @@ def main():
                                       "all_to_all routing from Python (%s)" % args.dist_backend)) if routed else
                                   ("one ctx, table hash-sharded over %d shards on this GPU (loopback routing)"
                                    % args.shards) if args.shards > 1 else "single GPU"},
-        "p50_batch_ms": float(np.percentile(lat, 50)), "p99_batch_ms": p99, "latency_batches": int(lat.size),
+        **({"p50_batch_ms": float(np.percentile(lat, 50)), "p99_batch_ms": p99, "latency_batches": int(lat.size)}
+           if args.full else {}),
         "host_submit_ms": round(host_submit_ms, 4),
         **({"p50_loaded_batch_ms": loaded["p50_ms"], "p99_loaded_batch_ms": loaded["p99_ms"],
             "loaded": loaded} if loaded else {}),
         "pcie_fed": pcie,
         "roofline": roofline, "cpu_baseline": cpu, "fill_s": round(t_fill, 2),
-        "verified": check["verified"], "self_check": check,
+        "full": args.full, "verified": check["verified"] if check else None, "self_check": check,
         **({"route_host_ms_per_step": route_host} if py_route else {}),
     }
     print(json.dumps(line), flush=True)
     be.close()
     if routed:
         dist.destroy_process_group()
+
+
+def dump_outputs(d, out, rank):
+    """--dump-outputs: the last timed step's answers as the caller received
+    them, one float64 array per output (exact: u8 codes, u32 remaining and
+    reset, i64 stats counters far below 2^53): 25 MB at the default batch."""
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + (".npy" if rank == 0 else ".rank%d.npy" % rank)), v.astype(np.float64))
 
 
 def make_batches(args, W, rank, tenants, sampler):

@@ -9,7 +9,7 @@ for rep in $(seq $REPS); do
   for lib in "" "$@"; do
     for cfg in $CFGS; do
       tag=$(basename "${lib:-cur}" .so)_${cfg}_$rep
-      RL_LIB_PATH=${lib:+$PWD/$lib} timeout -k 10 240 python -u bench.py --config $cfg --no-cpu-baseline --steps 200 \
+      RL_LIB_PATH=${lib:+$PWD/$lib} timeout -k 10 240 python -u bench.py --full --config $cfg --no-cpu-baseline --steps 200 \
         --latency-steps 5 --loaded-steps 0 --pcie-steps 0 $BARGS > gpurun_out/ab/$tag.log 2>&1
       rc=$?
       if [ $rc -ne 0 ]; then  # (a probe build that skips work fails the self-check: report its unverified rate)

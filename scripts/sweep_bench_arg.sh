@@ -9,7 +9,7 @@ for rep in $(seq $REPS); do
   for v in $VALS; do
     for cfg in $CFGS; do
       tag=${FLAG#--}_${v}_${cfg}_$rep
-      timeout -k 10 300 python -u bench.py --config $cfg --no-cpu-baseline --steps 200 --latency-steps 5 --loaded-steps 0 \
+      timeout -k 10 300 python -u bench.py --full --config $cfg --no-cpu-baseline --steps 200 --latency-steps 5 --loaded-steps 0 \
         --pcie-steps 0 $FLAG $v > gpurun_out/sweep/$tag.log 2>&1 || { tail -5 gpurun_out/sweep/$tag.log; exit 1; }
       python - gpurun_out/sweep/$tag.log $tag <<'PY'
 import json, sys

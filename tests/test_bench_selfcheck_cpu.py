@@ -64,6 +64,29 @@ def test_selfcheck_fails_on_one_wrong_answer(field):
     assert not chk["verified"] and chk["mismatches"], chk
 
 
+def test_plain_run_drops_what_full_adds(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.latency_steps == a.loaded_steps == a.pcie_steps == 0 and a.no_cpu_baseline
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and a.latency_steps == 1000 and a.loaded_steps == 1000
+    assert a.pcie_steps == 60 and not a.no_cpu_baseline
+
+
+def test_dump_outputs_is_exact_float64(tmp_path):
+    out = {"code": np.array([1, 2, 255], np.uint8), "limit_remaining": np.array([0, 2**32 - 1, 7], np.uint32),
+           "reset_s": np.array([1, 60, 2**31], np.uint32), "stats": np.array([2**40 + 1, 0, 5], np.int64)}
+    bench.dump_outputs(str(tmp_path / "d"), out, 0)
+    bench.dump_outputs(str(tmp_path / "d"), out, 3)
+    for k, v in out.items():
+        for name in (k + ".npy", k + ".rank3.npy"):
+            got = np.load(str(tmp_path / "d" / name))
+            assert got.dtype == np.float64 and np.array_equal(got, v.astype(np.float64))
+            assert np.array_equal(got.astype(v.dtype), v)
+
+
 def test_cpu_share_reports_a_basis():
     s = bench.cpu_share()
     assert s["cores"] >= 1 and s["cores"] <= s["affinity_cpus"] and s["basis"]

@@ -213,20 +213,55 @@ def test_dockerfile_build_and_final_stages_share_the_rocm_base():
     assert "/ratelimit/third_party/ratelimit_hip/lib/" in dk
 
 
+def _hunks(patch):
+    """(target, [(old start, old lines)]) of a one-file unified diff: each
+    hunk's context and removed lines, i.e. what `patch` must find in the file."""
+    lines = open(os.path.join(GO, "patches", patch)).read().split("\n")
+    target = re.match(r"--- a/(\S+)", lines[0]).group(1)
+    assert re.match(r"\+\+\+ b/%s\b" % re.escape(target), lines[1]), lines[1]
+    hunks, i = [], 2
+    while i < len(lines) and lines[i].startswith("@@"):
+        m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", lines[i])
+        assert m, lines[i]
+        n_old, n_new = int(m.group(2) or 1), int(m.group(4) or 1)
+        old, new, i = [], 0, i + 1
+        while len(old) < n_old or new < n_new:
+            tag, text = lines[i][:1], lines[i][1:]
+            assert tag in (" ", "-", "+", "\\"), (patch, i, lines[i])
+            if tag in (" ", "-"):
+                old.append(text)
+            if tag in (" ", "+"):
+                new += 1
+            i += 1
+        assert len(old) == n_old and new == n_new, (patch, m.group(0))
+        hunks.append((int(m.group(1)), old))
+    assert hunks and all(not l for l in lines[i:]), (patch, lines[i:i + 3])
+    return target, hunks
+
+
 def test_patches_apply_to_the_reference():
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "src")):
-        pytest.skip("reference tree not present (GPU box)")
-    with tempfile.TemporaryDirectory() as d:
-        for rel in ("src/settings/settings.go", "src/service_cmd/runner/runner.go", "Dockerfile",
-                    "src/service/ratelimit.go"):
-            os.makedirs(os.path.join(d, os.path.dirname(rel)), exist_ok=True)
-            with open(os.path.join(ref, rel)) as f, open(os.path.join(d, rel), "w") as g:
-                g.write(f.read())
-        for p in ("settings.go.patch", "runner.go.patch", "Dockerfile.patch", "ratelimit.go.patch"):
-            r = subprocess.run(["patch", "-p1", "--dry-run", "-d", d, "-i", os.path.join(GO, "patches", p)],
-                               capture_output=True, text=True)
-            assert r.returncode == 0, (p, r.stdout, r.stderr)
+    """Every hunk of go/patches/*.patch finds all its context and removed
+    lines, unchanged and in order, in the reference file it patches (no fuzz;
+    stricter than `patch --dry-run`). The reference files stand in as per-line
+    digests (tests/golden/ref_patch_targets.json, make_golden_patch_targets.py)."""
+    import hashlib
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "ref_patch_targets.json")) as f:
+        files = json.load(f)["files"]
+    seen = set()
+    for p in ("settings.go.patch", "runner.go.patch", "Dockerfile.patch", "ratelimit.go.patch"):
+        target, hunks = _hunks(p)
+        ref = files[target]
+        seen.add(target)
+        at = 0  # hunks apply top to bottom, none over the one before
+        for start, old in hunks:
+            want = [hashlib.sha256(l.encode()).hexdigest()[:16] for l in old]
+            found = [k for k in range(at, len(ref) - len(want) + 1) if ref[k:k + len(want)] == want]
+            assert found, "%s: the hunk at line %d does not apply to %s" % (p, start, target)
+            # at its stated line, or (as `patch` does) the nearest place where it applies
+            k = min(found, key=lambda k: abs(k - (start - 1)))
+            at = k + len(want)
+    assert seen == set(files), seen ^ set(files)
 
 
 def test_integration_md_points_at_the_go_files():
