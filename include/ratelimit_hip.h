@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RL_ABI_VERSION 6u
+#define RL_ABI_VERSION 7u
 
 /* Status codes. */
 enum rl_status {
@@ -644,6 +644,69 @@ int rl_local_cache_info_get(rl_ctx* ctx, int64_t now, rl_local_cache_info* info)
 int rl_snapshot_size(rl_ctx* ctx, uint64_t* bytes);
 int rl_snapshot_save(rl_ctx* ctx, void* host, uint64_t bytes);
 int rl_snapshot_load(rl_ctx* ctx, const void* host, uint64_t bytes);
+
+/* ---- Export / import of live counters (resize, reshard, re-key) -------------
+ * A snapshot is an exact image: it loads only into a ctx of the same shape and
+ * hash key. rl_export_range turns the live state into portable records, one
+ * per Redis key (stem, unit, window start), and rl_import writes such records
+ * into ANY ctx: other table_slots, history_entries, hash_seed or n_shards (the
+ * Redis side of the reference: keys can be scanned, dumped and migrated, and a
+ * cluster reshards under load, src/redis/driver_impl.go:108-126).
+ *
+ * rl_export_range orders after every submitted batch and is read-only. It
+ * emits every window record of every live slot in [slot_begin, slot_end)
+ * (clamped to shard_slots) of shard `shard`: the slot's newest window and the
+ * newest version of each older window on its history chain. The records of one
+ * (stem, unit) are contiguous, oldest window first; the order between keys is
+ * unspecified. A slot is a key, so ranges that tile [0, shard_slots) yield
+ * every key exactly once. Where a key's chain ends in an entry the log
+ * overwrote or refused, its oldest emitted record carries RL_REC_CHAIN_LOST:
+ * older windows may have had records (a request for one is RL_E_TIME, before
+ * and after a move). out == NULL: only *info is filled (sizing). An `out` too
+ * small for the range (records, or stem bytes, or a range holding 4 GiB of
+ * stems or more: stem_off is 32-bit per call) gives RL_E_CAPACITY with
+ * info->records / info->stem_bytes = what the range needs, and writes nothing.
+ * Not on a ctx that joined a communicator (RL_E_INVALID).
+ *
+ * rl_import performs, per record, a raw SET of that one (stem, unit, window)
+ * record: count, expire and lc verbatim (no clock, no fan-out to the records
+ * of other units: the export carries those separately). in->n <= max_batch and
+ * the stem bytes <= max_stem_bytes (RL_E_CAPACITY); a unit outside 1..4, a ws
+ * that is no multiple of the unit's divider or above 2^32 - 172801, an empty
+ * stem or one over 65535 bytes, or bad offsets give RL_E_INVALID and leave the
+ * table untouched. Records of one key arrive oldest first (over one or several
+ * calls): each newer window becomes the key's newest and the previous one goes
+ * to this ctx's history log under its own horizon. RL_REC_CHAIN_LOST on the
+ * first record of a key this ctx does not hold yet ends the key's chain in a
+ * lost entry; on a key it holds the flag is ignored and the record overwrites
+ * that window. New keys claim slots (and arena space) as requests do
+ * (RL_E_TABLE_FULL / RL_E_ARENA_FULL). A multi-shard ctx routes the records to
+ * their owners on the host. The sweep floor, the local-cache gauges and the
+ * batches / decisions counters are left alone. */
+#define RL_REC_CHAIN_LOST 0x1u
+typedef struct rl_records {      /* host memory; one record per (stem, unit, window) */
+  uint32_t n;          /* export: in = capacity in records, out = records written; import: records */
+  uint32_t reserved;
+  uint64_t stem_cap;   /* export: capacity of stem_bytes (import: ignored) */
+  uint8_t* stem_bytes;
+  uint32_t* stem_off;  /* n + 1, stem_off[0] == 0 */
+  uint8_t* unit;       /* rl_unit */
+  uint8_t* flags;      /* RL_REC_* */
+  uint32_t* ws;        /* window start (the Redis key's suffix) */
+  uint32_t* count;     /* INCRBY value */
+  uint32_t* expire;    /* key live while now <= expire */
+  uint32_t* lc;        /* local over-limit cache entry live while now < lc (0: none) */
+} rl_records;
+typedef struct rl_export_info {
+  uint64_t shard_slots;  /* slots of this shard's table (the scan's upper bound) */
+  uint64_t records, stem_bytes;  /* what the range holds (on RL_E_CAPACITY: what it needs) */
+  uint64_t keys;         /* live (stem, unit) slots in the range */
+  uint64_t chains_lost;  /* keys whose history chain ended at an overwritten or refused entry */
+  int64_t time_floor;    /* the ctx's sweep floor */
+} rl_export_info;
+int rl_export_range(rl_ctx* ctx, uint32_t shard, uint64_t slot_begin, uint64_t slot_end, rl_records* out,
+                    rl_export_info* info);
+int rl_import(rl_ctx* ctx, const rl_records* in);
 
 /* Per-stage device timing (HIP events on the batch stream), for benchmarks.
  * rl_profile(ctx, k) with k >= 1 starts accumulating over every k-th batch,

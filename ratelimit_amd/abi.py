@@ -122,6 +122,24 @@ class RlLocalCacheInfo(C.Structure):
                 ("miss_count", C.c_uint64)]
 
 
+RL_REC_CHAIN_LOST = 1  # rl_records.flags: older windows of the key may have had records the log lost
+
+
+class RlRecords(C.Structure):
+    """rl_records: portable window records, one per (stem, unit, window) (rl_export_range / rl_import)."""
+    _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("stem_cap", C.c_uint64), ("stem_bytes", P),
+                ("stem_off", P), ("unit", P), ("flags", P), ("ws", P), ("count", P), ("expire", P), ("lc", P)]
+
+
+class RlExportInfo(C.Structure):
+    _fields_ = [("shard_slots", C.c_uint64), ("records", C.c_uint64), ("stem_bytes", C.c_uint64),
+                ("keys", C.c_uint64), ("chains_lost", C.c_uint64), ("time_floor", C.c_int64)]
+
+
+# the per-record arrays of rl_records (stem_bytes / stem_off apart)
+RECORD_DTYPES = {"unit": np.uint8, "flags": np.uint8, "ws": np.uint32, "count": np.uint32,
+                 "expire": np.uint32, "lc": np.uint32}
+
 RL_MATCH_NONE, RL_MATCH_UNLIMITED, RL_MATCH_LIMIT = 0, 1, 2
 REQUEST_ARRAYS = ("domain_bytes", "domain_off", "now", "hits", "req_idx", "entry_first", "desc_off", "desc_bytes",
                   "key_len", "value_len", "override_flags", "override_rpu", "override_unit", "override_rule")
@@ -149,7 +167,7 @@ BATCH_DTYPES = {"stem_bytes": np.uint8, "stem_off": np.uint32, "now": np.int64, 
                 "rule_id": np.uint32}
 RESULT_DTYPES = {"code": np.uint8, "limit_remaining": np.uint32, "reset_s": np.uint32, "stats": np.uint64,
                  "status": np.uint8}
-ABI_VERSION = 6
+ABI_VERSION = 7
 RL_COMM_ID_BYTES = 128  # include/ratelimit_hip.h
 RL_ROUTED_INFLIGHT = 6  # include/ratelimit_hip.h (routed batches in flight: the input-reuse distance)
 RL_ROUTED_LAG = 3  # include/ratelimit_hip.h (calls between a routed batch's partition and its owner pipeline)

@@ -767,6 +767,59 @@ int rl_snapshot_load(rl_ctx* c, const void* host, uint64_t bytes) {
   return RL_OK;
 }
 
+int rl_export_range(rl_ctx* c, uint32_t shard, uint64_t slot_begin, uint64_t slot_end, rl_records* out,
+                    rl_export_info* info) {
+  if (!c || !info) return fail(c, RL_E_INVALID, "gpu: null argument");
+  if (c->comm) return fail(c, RL_E_INVALID, "gpu: rl_export_range is not for a ctx that joined a communicator");
+  if (shard >= c->n) return fail(c, RL_E_INVALID, "gpu: bad shard");
+  if (const int src = settle_local(c)) return src;
+  return from_engine(c, c->e[shard], eng_export_range(c->e[shard], slot_begin, slot_end, out, info));
+}
+
+int rl_import(rl_ctx* c, const rl_records* in) {
+  if (!c || !in) return fail(c, RL_E_INVALID, "gpu: null argument");
+  if (c->comm) return fail(c, RL_E_INVALID, "gpu: rl_import is not for a ctx that joined a communicator");
+  if (const int src = settle_local(c)) return src;
+  if (c->n == 1) return eng_import(c->e[0], in);
+  // the whole call is checked first (a bad record leaves every shard untouched),
+  // then the records go to their owners, routed on the host like rl_restore's
+  if (const int rc = from_engine(c, c->e[0], eng_import_check(c->e[0], in))) return rc;
+  const uint32_t N = c->n;
+  std::vector<std::vector<uint32_t>> idx(N);
+  for (uint32_t i = 0; i < in->n; i++) {
+    const uint32_t a = in->stem_off[i], b = in->stem_off[i + 1];
+    idx[owner_of_host(hash_stem_host(c->e[0]->hk, in->stem_bytes + a, b - a), N)].push_back(i);
+  }
+  for (uint32_t j = 0; j < N; j++) {
+    if (idx[j].empty()) continue;
+    std::vector<uint8_t> stems, unit, flags;
+    std::vector<uint32_t> off{0}, ws, count, expire, lc;
+    for (uint32_t i : idx[j]) {
+      stems.insert(stems.end(), in->stem_bytes + in->stem_off[i], in->stem_bytes + in->stem_off[i + 1]);
+      off.push_back((uint32_t)stems.size());
+      unit.push_back(in->unit[i]);
+      flags.push_back(in->flags ? in->flags[i] : 0);
+      ws.push_back(in->ws[i]);
+      count.push_back(in->count[i]);
+      expire.push_back(in->expire[i]);
+      lc.push_back(in->lc[i]);
+    }
+    rl_records sub{};
+    sub.n = (uint32_t)idx[j].size();
+    sub.stem_bytes = stems.data();
+    sub.stem_off = off.data();
+    sub.unit = unit.data();
+    sub.flags = flags.data();
+    sub.ws = ws.data();
+    sub.count = count.data();
+    sub.expire = expire.data();
+    sub.lc = lc.data();
+    const int rc = from_engine(c, c->e[j], eng_import(c->e[j], &sub));
+    if (rc) return rc;
+  }
+  return RL_OK;
+}
+
 int rl_config_load(rl_ctx* c, const rl_config_tree* t) {
   if (!c) return fail(c, RL_E_INVALID, "gpu: null ctx");
   if (c->n > 1 && t && t->nodes)  // (the shards' own check allows their n x max_rules rows)

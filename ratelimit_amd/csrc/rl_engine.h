@@ -219,6 +219,12 @@ int eng_local_cache_info_get(Engine* c, int64_t now, rl_local_cache_info* info);
 int eng_snapshot_size(Engine* c, uint64_t* bytes);
 int eng_snapshot_save(Engine* c, void* host, uint64_t bytes);
 int eng_snapshot_load(Engine* c, const void* host, uint64_t bytes);
+// rl_export_range on this engine's table (out == null: *info only).
+int eng_export_range(Engine* c, uint64_t slot_begin, uint64_t slot_end, rl_records* out, rl_export_info* info);
+// rl_import's checks of a whole call against this engine's limits (host only);
+// eng_import runs them too.
+int eng_import_check(Engine* c, const rl_records* in);
+int eng_import(Engine* c, const rl_records* in);
 
 // Owner side of a routed batch, pipelined on the engine's streams like
 // eng_do_limit_async: unpack the n received wire records (chunks of n_src

@@ -1817,6 +1817,184 @@ int eng_snapshot_load(Engine* c, const void* host, uint64_t bytes) {
   return RL_OK;
 }
 
+namespace {
+
+// Device memory of one call, freed when it returns.
+struct DevBufs {
+  std::vector<void*> p;
+  ~DevBufs() {
+    for (void* q : p) (void)hipFree(q);
+  }
+  template <typename T>
+  hipError_t get(T** out, size_t count) {
+    const hipError_t e = dalloc(out, count);
+    if (e == hipSuccess) p.push_back(*out);
+    return e;
+  }
+};
+
+}  // namespace
+
+int eng_export_range(Engine* c, uint64_t s0, uint64_t s1, rl_records* out, rl_export_info* info) {
+  if (!c || !info) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (out && (!out->stem_off || (out->n && (!out->unit || !out->flags || !out->ws || !out->count || !out->expire ||
+                                            !out->lc)) ||
+              (out->stem_cap && !out->stem_bytes)))
+    return set_err(c, RL_E_INVALID, "gpu: null rl_records array");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream;
+  HIPCHK(c, after_batches(c, st));
+  s1 = std::min<uint64_t>(s1, c->nslots);
+  s0 = std::min(s0, s1);
+  *info = rl_export_info{};
+  info->shard_slots = c->nslots;
+  HIPCHK(c, hipMemcpyAsync(&info->time_floor, c->s[0].time_floor, 8, hipMemcpyDeviceToHost, st));
+  DevBufs mem;
+  uint32_t* cnt = nullptr;
+  unsigned long long* tot = nullptr;  // [0..3] the range's sums, [4] the write cursor
+  unsigned long long h_tot[5] = {};
+  if (s1 > s0) {
+    HIPCHK(c, mem.get(&cnt, s1 - s0));
+    HIPCHK(c, mem.get(&tot, 5));
+    HIPCHK(c, hipMemsetAsync(tot, 0, 40, st));
+    launch_export_count(table_view(c), s0, s1, cnt, tot, st);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_tot, tot, 40, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  const uint64_t nrec = h_tot[0], nb = h_tot[1];
+  info->records = nrec;
+  info->stem_bytes = nb;
+  info->keys = h_tot[2];
+  info->chains_lost = h_tot[3];
+  if (!out) return RL_OK;
+  // (stem_off is 32-bit per call: a range holding 4 GiB of stems goes out in smaller ranges)
+  if (nrec > out->n || nb > out->stem_cap || nb > 0xFFFFFFFFull)
+    return set_err(c, RL_E_CAPACITY,
+                   "gpu: export range holds " + std::to_string(nrec) + " records / " + std::to_string(nb) +
+                       " stem bytes: larger than rl_records (or 4 GiB of stems: export smaller ranges)");
+  out->n = (uint32_t)nrec;
+  out->stem_off[0] = 0;
+  if (!nrec) return RL_OK;
+  ExportDev o{};
+  HIPCHK(c, mem.get(&o.stem, nb));
+  HIPCHK(c, mem.get(&o.off, nrec));
+  HIPCHK(c, mem.get(&o.unit, nrec));
+  HIPCHK(c, mem.get(&o.flags, nrec));
+  HIPCHK(c, mem.get(&o.ws, nrec));
+  HIPCHK(c, mem.get(&o.count, nrec));
+  HIPCHK(c, mem.get(&o.expire, nrec));
+  HIPCHK(c, mem.get(&o.lc, nrec));
+  launch_export_write(table_view(c), s0, s1, cnt, tot + 4, o, st);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out->stem_bytes, o.stem, nb, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->stem_off, o.off, nrec * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->unit, o.unit, nrec, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->flags, o.flags, nrec, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->ws, o.ws, nrec * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->count, o.count, nrec * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->expire, o.expire, nrec * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->lc, o.lc, nrec * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(h_tot + 4, tot + 4, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  out->stem_off[nrec] = (uint32_t)nb;
+  if (h_tot[4] != ((nrec << 32) | nb)) return set_err(c, RL_E_INTERNAL, "gpu: export wrote other than it counted");
+  return RL_OK;
+}
+
+int eng_import_check(Engine* c, const rl_records* in) {
+  if (!c || !in) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  const uint32_t n = in->n;
+  if (n > c->cfg.max_batch) return set_err(c, RL_E_CAPACITY, "gpu: import exceeds configured max_batch");
+  if (!n) return RL_OK;
+  if (!in->stem_bytes || !in->stem_off || !in->unit || !in->ws || !in->count || !in->expire || !in->lc)
+    return set_err(c, RL_E_INVALID, "gpu: null rl_records array");
+  if (in->stem_off[0] != 0) return set_err(c, RL_E_INVALID, "gpu: import stem offsets must start at 0");
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t a = in->stem_off[i], b = in->stem_off[i + 1];
+    if (b <= a || b - a > 65535u)
+      return set_err(c, RL_E_INVALID, "gpu: import record " + std::to_string(i) + ": stem offsets (1..65535 bytes)");
+    const uint32_t u = in->unit[i];
+    if (u < 1 || u > 4) return set_err(c, RL_E_INVALID, "gpu: import record " + std::to_string(i) + ": unit outside 1..4");
+    if (in->ws[i] > NOW_MAX || in->ws[i] % div_of(u))
+      return set_err(c, RL_E_INVALID,
+                     "gpu: import record " + std::to_string(i) + ": ws is no window start of its unit (or > 2^32-172801)");
+  }
+  if (in->stem_off[n] > c->cfg.max_stem_bytes)
+    return set_err(c, RL_E_CAPACITY, "gpu: import exceeds configured max_stem_bytes");
+  return RL_OK;
+}
+
+int eng_import(Engine* c, const rl_records* in) {
+  if (const int rc = eng_import_check(c, in)) return rc;
+  const uint32_t n = in->n;
+  if (!n) return RL_OK;
+  // group the records by stem (a stem's records stay in arrival order): one
+  // lane of k_import takes a stem with all its units
+  std::vector<uint64_t> hash(n);
+  for (uint32_t i = 0; i < n; i++) {
+    uint64_t h = hash_stem_host(c->hk, in->stem_bytes + in->stem_off[i], in->stem_off[i + 1] - in->stem_off[i]);
+    if ((uint32_t)(h >> 32) == KEY_DUP) h = ((uint64_t)(KEY_DUP - 1u) << 32) | (uint32_t)h;  // (as k_prepare homes it)
+    hash[i] = h;
+  }
+  auto stem_cmp = [&](uint32_t x, uint32_t y) {
+    const uint32_t lx = in->stem_off[x + 1] - in->stem_off[x], ly = in->stem_off[y + 1] - in->stem_off[y];
+    if (lx != ly) return lx < ly ? -1 : 1;
+    return memcmp(in->stem_bytes + in->stem_off[x], in->stem_bytes + in->stem_off[y], lx);
+  };
+  std::vector<uint32_t> order(n);
+  for (uint32_t i = 0; i < n; i++) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+    if (hash[x] != hash[y]) return hash[x] < hash[y];
+    const int k = stem_cmp(x, y);
+    return k ? k < 0 : x < y;
+  });
+  std::vector<ImportRec> rec(n);
+  std::vector<uint32_t> gstart;
+  std::vector<unsigned long long> ghash;
+  for (uint32_t j = 0; j < n; j++) {
+    const uint32_t i = order[j];
+    if (!j || hash[i] != hash[order[j - 1]] || stem_cmp(i, order[j - 1])) {
+      gstart.push_back(j);
+      ghash.push_back(hash[i]);
+    }
+    ImportRec& r = rec[j];
+    r.off = in->stem_off[i];
+    r.lu = (in->stem_off[i + 1] - in->stem_off[i]) | ((uint32_t)in->unit[i] << 16) |
+           ((uint32_t)((in->flags ? in->flags[i] : 0) & RL_REC_CHAIN_LOST) << 24);
+    r.ws = in->ws[i];
+    r.count = in->count[i];
+    r.expire = in->expire[i];
+    r.lc = in->lc[i];
+    r.pad[0] = r.pad[1] = 0;
+  }
+  gstart.push_back(n);
+  const uint32_t ng = (uint32_t)ghash.size(), nb = in->stem_off[n];
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream;
+  HIPCHK(c, after_batches(c, st));
+  DevBufs mem;
+  uint8_t* d_stem = nullptr;
+  ImportRec* d_rec = nullptr;
+  uint32_t *d_gs = nullptr, *d_err = nullptr;
+  unsigned long long *d_gh = nullptr, *d_epoch = nullptr;
+  HIPCHK(c, mem.get(&d_stem, (size_t)nb + 64));
+  HIPCHK(c, mem.get(&d_rec, n));
+  HIPCHK(c, mem.get(&d_gs, (size_t)ng + 1));
+  HIPCHK(c, mem.get(&d_gh, ng));
+  HIPCHK(c, mem.get(&d_epoch, LOG_PARTS));
+  HIPCHK(c, mem.get(&d_err, 1));
+  HIPCHK(c, hipMemcpyAsync(d_stem, in->stem_bytes, nb, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_rec, rec.data(), (size_t)n * sizeof(ImportRec), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_gs, gstart.data(), ((size_t)ng + 1) * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_gh, ghash.data(), (size_t)ng * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(d_err, 0, 4, st));
+  launch_import(table_view(c), c->hk, d_stem, nb, d_rec, d_gs, d_gh, ng, d_epoch, d_err, st);
+  HIPCHK(c, hipGetLastError());
+  uint32_t e = 0;
+  HIPCHK(c, hipMemcpyAsync(&e, d_err, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return map_err(c, e);
+}
+
 }  // namespace rl
-
-

@@ -378,6 +378,39 @@ void launch_arena_compact(Slot* slots, uint64_t nslots, const uint8_t* from, uin
                           hipStream_t st);
 void launch_lc_count(const TableDev& t, uint64_t nslots, uint32_t now, unsigned long long* out, hipStream_t st);
 void launch_table_info(const Slot* slots, uint64_t nslots, unsigned long long* out, hipStream_t st);
+// ---- export / import of window records (rl_export_range, rl_import) ----
+// Device staging of one export call: the rl_records arrays (off: the records'
+// stem offsets; the host appends the total).
+struct ExportDev {
+  uint8_t* stem;
+  uint32_t* off;
+  uint8_t* unit;
+  uint8_t* flags;
+  uint32_t *ws, *count, *expire, *lc;
+};
+// The slots [s0, s1): cnt[i - s0] = slot i's records (bit 31: its chain broke),
+// tot[0..3] += records, stem bytes, live slots, broken chains.
+void launch_export_count(const TableDev& t, uint64_t s0, uint64_t s1, uint32_t* cnt, unsigned long long* tot,
+                         hipStream_t st);
+// ... written out, each key's records contiguous and oldest first. *cursor
+// (zero on entry) ends as records << 32 | stem bytes: both must stay below 2^32.
+void launch_export_write(const TableDev& t, uint64_t s0, uint64_t s1, const uint32_t* cnt, unsigned long long* cursor,
+                         const ExportDev& o, hipStream_t st);
+// One record of an import call, the call's records grouped by stem on the host.
+struct __attribute__((aligned(16))) ImportRec {
+  uint32_t off;  // stem byte offset
+  uint32_t lu;   // stem length (16) | unit << 16 | RL_REC_* flags << 24
+  uint32_t ws, count, expire, lc;
+  uint32_t pad[2];
+};
+static_assert(sizeof(ImportRec) == 32, "ImportRec is two dwordx4");
+// Raw SET of the records rec[gstart[g], gstart[g + 1]) of stem group g < ng
+// (one stem each, hash ghash[g], no stem in two groups; records in arrival
+// order), stems in `stem` (16-B aligned, readable to the next 16-B boundary
+// past stem_total). epoch: [LOG_PARTS] scratch. Device errors are ORed into *err.
+void launch_import(const TableDev& t, const HashKey& hk, const uint8_t* stem, uint32_t stem_total, const ImportRec* rec,
+                   const uint32_t* gstart, const unsigned long long* ghash, uint32_t ng, unsigned long long* epoch,
+                   uint32_t* err, hipStream_t st);
 // Built with RL_LOG_TEAR (rl_debug_log_tear's hook in the history log's lookups)?
 bool log_tear_hook();
 void launch_debug_keys(const BatchDev& b, uint8_t* out, uint32_t* klen, hipStream_t st);

@@ -5124,6 +5124,274 @@ __global__ __launch_bounds__(256) void k_table_info(const Slot* slots, uint64_t 
 }
 
 // ===========================================================================
+// Export / import of window records (rl_export_range, rl_import): the live
+// state as portable (stem, unit, window) records, and a raw SET of such
+// records into a table of any geometry, hash key and shard layout.
+//
+// The export is a scan, one lane per slot of the range, each reading its
+// slot's whole 64-B sector (uint4 x 4, coalesced, as a probe does). A slot's
+// records are its cur and, per older window, the newest version on its history
+// chain. The chain is walked under log_find's checks (owner slot and tag,
+// non-increasing t_app, Brent's cycle check, LOG_MAX_HOPS, a position past the
+// partition, LOG_LOST); nothing writes during the scan, so plain loads do. A
+// walk that breaks marks the key's oldest record RL_REC_CHAIN_LOST; only
+// entries reached before the break (all proven the slot's own) are emitted.
+// Two passes: k_export_count sums records, stem bytes, keys and lost chains of
+// the range and keeps each slot's record count; the host checks the caller's
+// capacity from the sums; k_export_write then reserves each workgroup's output
+// positions with ONE atomic (records in the high word, stem bytes in the low
+// one: a record's stem offset and its index come from the same reservation, so
+// the offsets rise with the index) and every lane writes its key's records
+// oldest first: per record one more walk picks the smallest window above the
+// last one written, the version nearest the head (chains are bounded by the
+// reach rules: a handful of entries).
+// ===========================================================================
+template <typename F>
+__device__ inline bool export_walk(const TableDev& t, uint32_t si, const SlotImg& im, F f) {
+  uint32_t ptr = im.ring(), tprev = im.cur().ws, saved = LOG_NONE, power = 1, lam = 0;
+  for (uint32_t hops = 0; ptr != LOG_NONE; hops++) {
+    const uint32_t pos = ptr & LOG_POS_MASK;
+    if (hops == LOG_MAX_HOPS || pos >= t.log_cap || ptr == saved) return false;
+    if (++lam == power) {
+      saved = ptr;
+      power <<= 1;
+      lam = 0;
+    }
+    const uint4* e = reinterpret_cast<const uint4*>(&t.log[(size_t)(ptr >> LOG_POS_BITS) * t.log_cap + pos]);
+    const uint4 a = e[0], b = e[1];
+    // overwritten (owner, order), or no record of a window below its t_app
+    if (a.x != si || a.y != im.tag() || a.w > tprev || b.x >= a.w) return false;
+    f(Win{b.x, b.y, b.z, b.w});
+    tprev = a.w;
+    ptr = a.z;
+  }
+  return true;
+}
+
+// The newest version of the smallest logged window of slot si above lo (any:
+// the smallest of all). False: none. *lost: the walk broke.
+__device__ inline bool export_next(const TableDev& t, uint32_t si, const SlotImg& im, bool any, uint32_t lo, Win* out,
+                                   bool* lost) {
+  Win best{WS_INVALID, 0, 0, 0};
+  const uint32_t cw = im.cur().ws;
+  *lost = !export_walk(t, si, im, [&](const Win& w) {
+    if (w.ws >= cw) return;  // (cur is the key's newest window)
+    if ((any || w.ws > lo) && w.ws < best.ws) best = w;  // (<: among versions of one window, the first met)
+  });
+  *out = best;
+  return best.ws != WS_INVALID;
+}
+
+constexpr uint32_t EXPORT_LOST = 0x80000000u;  // k_export_count's per-slot word: records | EXPORT_LOST
+
+// tot: [0] records, [1] stem bytes, [2] keys, [3] chains lost. Grid-stride, the
+// sums kept per lane and folded per workgroup: one atomic per counter and
+// workgroup (a wave's own atomics, 2^16 of them on one line for a range of
+// 2^22 slots, took longer than the scan itself).
+__global__ __launch_bounds__(256) void k_export_count(const TableDev t, uint64_t s0, uint64_t s1,
+                                                      uint32_t* __restrict__ cnt, unsigned long long* tot) {
+  unsigned long long v[4] = {0, 0, 0, 0};
+  for (uint64_t i = s0 + blockIdx.x * 256ull + threadIdx.x; i < s1; i += (uint64_t)gridDim.x * 256) {
+    SlotImg im;
+    load_img_lo(&t.slots[i], im);
+    uint32_t r = 0;
+    bool lost = false;
+    if (im.tag() >= 2) {
+      bool brk = false;
+      Win w{WS_INVALID, 0, 0, 0};
+      for (bool any = true; export_next(t, (uint32_t)i, im, any, w.ws, &w, &brk); any = false) r++;
+      if (im.cur().ws != WS_INVALID) r++;
+      lost = brk && r;
+      v[0] += r;
+      v[1] += (unsigned long long)r * im.key_len();
+      v[2] += 1;
+      v[3] += lost;
+    }
+    cnt[i - s0] = r | (lost ? EXPORT_LOST : 0u);
+  }
+  __shared__ unsigned long long sh[4][4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const unsigned long long x = wave_sum(v[k]);
+    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6][k] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const unsigned long long x = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    if (x) atomicAdd(&tot[threadIdx.x], x);
+  }
+}
+
+// A slot's whole stem: its inline bytes, then (longer than KEY_IN) the arena's.
+__device__ inline void export_stem(const TableDev& t, const Slot* s, uint32_t len, uint8_t* dst) {
+  const uint32_t il = slot_inline(len);
+  for (uint32_t k = 0; k < il; k++) dst[k] = s->key[k];
+  if (len > KEY_IN) {
+    const uint8_t* ek = t.arena + (size_t)slot_ext(s) * 16;
+    for (uint32_t k = KEY_SPLIT; k < len; k++) dst[k] = ek[k - KEY_SPLIT];
+  }
+}
+
+// cursor: records << 32 | stem bytes reserved so far (the host made sure both
+// stay below 2^32 for the whole range, so the low word never carries). One
+// atomic per workgroup of EXPORT_WRITE_THREADS lanes: an inclusive scan of
+// (records, bytes) inside each wave, the waves' totals scanned through LDS.
+constexpr uint32_t EXPORT_WRITE_THREADS = 1024;
+__global__ __launch_bounds__(EXPORT_WRITE_THREADS) void k_export_write(const TableDev t, uint64_t s0, uint64_t s1,
+                                                                       const uint32_t* __restrict__ cnt,
+                                                                       unsigned long long* cursor, const ExportDev o) {
+  const uint64_t i = s0 + (uint64_t)blockIdx.x * EXPORT_WRITE_THREADS + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t c = i < s1 ? cnt[i - s0] : 0u, r = c & ~EXPORT_LOST;
+  SlotImg im;
+  uint32_t len = 0;
+  if (r) {
+    load_img_lo(&t.slots[i], im);
+    len = im.key_len();
+  }
+  const unsigned long long mine = ((unsigned long long)r << 32) | ((unsigned long long)r * len);
+  unsigned long long x = mine;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const unsigned long long y = __shfl_up(x, d);
+    if (lane >= d) x += y;
+  }
+  __shared__ unsigned long long wtot[EXPORT_WRITE_THREADS / 64];
+  if (lane == 63) wtot[wave] = x;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long run = 0;
+    for (uint32_t k = 0; k < EXPORT_WRITE_THREADS / 64; k++) {
+      const unsigned long long w = wtot[k];
+      wtot[k] = run;  // (exclusive: the waves before k)
+      run += w;
+    }
+    const unsigned long long at0 = run ? atomicAdd(cursor, run) : 0ull;
+    for (uint32_t k = 0; k < EXPORT_WRITE_THREADS / 64; k++) wtot[k] += at0;
+  }
+  __syncthreads();
+  const unsigned long long base = wtot[wave];
+  if (!r) return;
+  const unsigned long long at = base + x - mine;
+  uint32_t R = (uint32_t)(at >> 32), B = (uint32_t)at;
+  const Slot* s = &t.slots[i];
+  const uint8_t unit = (uint8_t)im.unit();
+  auto put = [&](const Win& w, uint32_t j) {
+    o.off[R] = B;
+    o.unit[R] = unit;
+    o.flags[R] = (uint8_t)((c & EXPORT_LOST) && j == 0 ? RL_REC_CHAIN_LOST : 0u);
+    o.ws[R] = w.ws;
+    o.count[R] = w.count;
+    o.expire[R] = w.expire;
+    o.lc[R] = w.lc;
+    export_stem(t, s, len, o.stem + B);
+    R++;
+    B += len;
+  };
+  const bool has_cur = im.cur().ws != WS_INVALID;
+  const uint32_t logged = r - (has_cur ? 1u : 0u);
+  Win w{WS_INVALID, 0, 0, 0};
+  bool brk;
+  uint32_t j = 0;
+  for (; j < logged && export_next(t, (uint32_t)i, im, j == 0, w.ws, &w, &brk); j++) put(w, j);
+  if (has_cur && j == logged) put(im.cur(), j);
+}
+
+// This call's floor of the history log's append counters (log_append's bound).
+__global__ __launch_bounds__(256) void k_log_epoch(const unsigned long long* log_ctr,
+                                                   unsigned long long* __restrict__ epoch) {
+  if (threadIdx.x < LOG_PARTS)
+    epoch[threadIdx.x] =
+        __hip_atomic_load(log_ctr + (size_t)threadIdx.x * LOG_CTR_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The import: one lane per stem. The host groups the call's records by stem
+// (a stem's records stay in their order), so no two lanes ever hold the same
+// (stem, unit), a lane sees every unit of its stem that the call carries, and
+// concurrent inserts of different stems meet only in slot_claim's CAS, as in
+// the batch kernels. Per record a raw SET of the (stem, unit, window) record:
+//  - a window above the slot's cur becomes cur, the old cur goes to the log if
+//    THIS table would keep it (hist_keep under its own horizon);
+//  - cur's own window is overwritten;
+//  - a window below cur is appended as the newest version of that window.
+// RL_REC_CHAIN_LOST on the record that inserts a key makes LOG_LOST the end of
+// its chain. A stem that ends up with two or more unit slots gets SLOT_EXACT
+// on all of them (stem_exact's rule).
+constexpr int64_t SLOT_UNKNOWN = -9;
+// log_append for the import, into partition p: a lane imports its stem's
+// records one after the other, so log_append's partition per wave would send
+// a call's appends (up to max_batch) to the few partitions of its few waves,
+// which then wrap onto, or refuse, the records just imported. One atomic per
+// append instead (imports are rare); the caller spreads p over the partitions,
+// and a call's appends then stay below any partition's log_cap (>= max_batch
+// / 16). The entry is published as log_append publishes it.
+__device__ inline uint32_t import_append(const TableDev& t, uint32_t p, uint32_t si, uint32_t tag, uint32_t prev,
+                                         uint32_t t_app, const Win& r) {
+  const unsigned long long k = atomicAdd(&t.log_ctr[(size_t)p * LOG_CTR_STRIDE], 1ull);
+  if (k - t.log_epoch[p] >= t.log_cap) {
+    atomicAdd(t.hist_lost + 1, 1ull);
+    return LOG_LOST;
+  }
+  const uint32_t pos = (uint32_t)k & (t.log_cap - 1u);
+  uint4* e = reinterpret_cast<uint4*>(&t.log[(size_t)p * t.log_cap + pos]);
+  const uint4 h = make_uint4(si, tag, prev, t_app), rv = make_uint4(r.ws, r.count, r.expire, r.lc);
+#pragma unroll
+  for (uint32_t s = 0; s < LOG_WRITE_STEPS; s++) log_write_step(e, s, h, rv, !RL_LOG_BUSY);
+  return (p << LOG_POS_BITS) | pos;
+}
+
+__global__ __launch_bounds__(256) void k_import(const TableDev t, const BatchDev b, const ImportRec* __restrict__ rec,
+                                                const uint32_t* __restrict__ gstart,
+                                                const unsigned long long* __restrict__ ghash, uint32_t ng,
+                                                uint32_t* err) {
+  const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= ng) return;
+  const uint64_t hs = ghash[g];
+  const uint32_t p0 = gstart[g], p1 = gstart[g + 1];
+  Rec r0{};
+  r0.off = rec[p0].off;
+  r0.lu = rec[p0].lu & 0xFFFFu;
+  const Key key = key_of(b, r0);
+  int64_t sidx[4] = {SLOT_UNKNOWN, SLOT_UNKNOWN, SLOT_UNKNOWN, SLOT_UNKNOWN};
+  bool ins;
+  for (uint32_t p = p0; p < p1; p++) {
+    const ImportRec x = rec[p];
+    const uint32_t u = (x.lu >> 16) & 0xFFu, d = div_of(u), tag = slot_tag(hs, u);
+    const uint32_t part = p & (LOG_PARTS - 1u);  // (the records' positions in the call: every partition alike)
+    bool fresh = false;
+    if (sidx[u - 1] == SLOT_UNKNOWN) {
+      sidx[u - 1] = find_slot(t, hs, tag, key, u, true, &ins, err);
+      fresh = ins;
+    }
+    if (sidx[u - 1] < 0) continue;  // (no slot: the error bit is set)
+    const uint32_t si = (uint32_t)sidx[u - 1];
+    Slot* s = &t.slots[si];
+    const Win cur = s->cur, nr{x.ws, x.count, x.expire, x.lc};
+    uint32_t chain = s->ring;
+    if (fresh && ((x.lu >> 24) & RL_REC_CHAIN_LOST)) {
+      chain = LOG_LOST;
+      s->ring = chain;
+    }
+    if (cur.ws == WS_INVALID || cur.ws == x.ws) {
+      s->cur = nr;
+    } else if (x.ws > cur.ws) {
+      if (hist_keep(t, cur, x.ws, d)) s->ring = import_append(t, part, si, tag, chain, x.ws, cur);
+      s->cur = nr;
+    } else {
+      s->ring = import_append(t, part, si, tag, chain, cur.ws, nr);
+    }
+  }
+  uint32_t present = 0;
+  for (uint32_t u = 1; u <= 4; u++) {
+    if (sidx[u - 1] == SLOT_UNKNOWN) sidx[u - 1] = find_slot(t, hs, slot_tag(hs, u), key, u, false, &ins, err);
+    if (sidx[u - 1] >= 0) present |= 1u << (u - 1);
+  }
+  if (__popc(present) >= 2)
+    for (uint32_t u = 0; u < 4; u++)
+      if ((present >> u) & 1) t.slots[sidx[u]].flags |= SLOT_EXACT;
+}
+
+// ===========================================================================
 // Diagnostics
 // ===========================================================================
 // Full Redis key stem ‖ strconv.FormatInt((now/div)*div, 10) into a padded
@@ -5323,6 +5591,34 @@ void launch_lc_count(const TableDev& t, uint64_t nslots, uint32_t now, unsigned 
 
 void launch_table_info(const Slot* slots, uint64_t nslots, unsigned long long* out, hipStream_t st) {
   k_table_info<<<2048, 256, 0, st>>>(slots, nslots, out);
+}
+
+void launch_export_count(const TableDev& t, uint64_t s0, uint64_t s1, uint32_t* cnt, unsigned long long* tot,
+                         hipStream_t st) {
+  if (s1 > s0)
+    k_export_count<<<(uint32_t)((s1 - s0 + 255) / 256 < 2048 ? (s1 - s0 + 255) / 256 : 2048), 256, 0, st>>>(t, s0, s1, cnt,
+                                                                                                          tot);
+}
+
+void launch_export_write(const TableDev& t, uint64_t s0, uint64_t s1, const uint32_t* cnt, unsigned long long* cursor,
+                         const ExportDev& o, hipStream_t st) {
+  if (s1 > s0)
+    k_export_write<<<(uint32_t)((s1 - s0 + EXPORT_WRITE_THREADS - 1) / EXPORT_WRITE_THREADS), EXPORT_WRITE_THREADS, 0,
+                     st>>>(t, s0, s1, cnt, cursor, o);
+}
+
+void launch_import(const TableDev& t, const HashKey& hk, const uint8_t* stem, uint32_t stem_total, const ImportRec* rec,
+                   const uint32_t* gstart, const unsigned long long* ghash, uint32_t ng, unsigned long long* epoch,
+                   uint32_t* err, hipStream_t st) {
+  if (!ng) return;
+  k_log_epoch<<<1, 256, 0, st>>>(t.log_ctr, epoch);
+  TableDev tv = t;
+  tv.log_epoch = epoch;
+  BatchDev b{};
+  b.hk = hk;
+  b.stem = stem;
+  b.stem_cap = b.stem_total = stem_total;
+  k_import<<<cdiv(ng, 256), 256, 0, st>>>(tv, b, rec, gstart, ghash, ng, err);
 }
 
 bool log_tear_hook() { return RL_LOG_TEAR != 0; }

@@ -30,7 +30,7 @@ from .types import OK, DescriptorStatus, Limit  # noqa: F401  (re-exported data 
 STAGES = ("prepare", "sort", "segment", "table", "finish")
 PROFILE_FIELDS = STAGES + ("table_kernel",)  # + k_table's own run time (device clock)
 
-__all__ = ["GpuRateLimitCache", "GpuRateLimitService", "RedisError", "TimeSource"]
+__all__ = ["GpuRateLimitCache", "GpuRateLimitService", "RedisError", "TimeSource", "migrate"]
 
 
 class TimeSource:
@@ -309,6 +309,89 @@ class Backend:
         buf = np.ascontiguousarray(buf, np.uint8)
         self._check(self.L.rl_snapshot_load(self.ctx, abi.ptr(buf), buf.size))
 
+    # ---- export / import of live counters (resize, reshard, re-key)
+    def n_shards(self) -> int:
+        return max(int(self.cfg.n_shards), 1)
+
+    def export_range(self, shard: int, slot_begin: int, slot_end: int, bufs: Optional[dict] = None):
+        """rl_export_range -> (records, info). records: numpy arrays stem_bytes,
+        stem_off (n + 1) and unit / flags / ws / count / expire / lc (n each), one
+        record per (stem, unit, window), a key's records contiguous and oldest
+        first; views of `bufs` (a dict this call fills and grows: pass the same one
+        to reuse the buffers, then copy what must outlive the next call). On
+        RL_E_CAPACITY the buffers grow to what info says and the range is retried once."""
+        bufs = bufs if bufs is not None else {}
+        info = abi.RlExportInfo()
+        for attempt in (0, 1):
+            cap = len(bufs["ws"]) if bufs else 0
+            if not bufs:
+                self._export_alloc(bufs, 4096, 1 << 18)
+                cap = 4096
+            r = abi.RlRecords()
+            r.n, r.stem_cap = cap, len(bufs["stem_bytes"])
+            for k in ("stem_bytes", "stem_off") + tuple(abi.RECORD_DTYPES):
+                setattr(r, k, abi.ptr(bufs[k]))
+            rc = self.L.rl_export_range(self.ctx, shard, slot_begin, slot_end, C.byref(r), C.byref(info))
+            if rc == abi.RL_E_CAPACITY and attempt == 0 and info.stem_bytes < 1 << 32:
+                self._export_alloc(bufs, max(cap, info.records), max(len(bufs["stem_bytes"]), info.stem_bytes))
+                continue
+            self._check(rc)
+            break
+        n = r.n
+        rec = {k: bufs[k][:n] for k in abi.RECORD_DTYPES}
+        rec["stem_off"] = bufs["stem_off"][:n + 1]
+        rec["stem_bytes"] = bufs["stem_bytes"][:int(bufs["stem_off"][n])]
+        return rec, {f: getattr(info, f) for f, _ in abi.RlExportInfo._fields_}
+
+    @staticmethod
+    def _export_alloc(bufs: dict, n: int, stem_cap: int) -> None:
+        bufs["stem_bytes"] = np.zeros(max(int(stem_cap), 1), np.uint8)
+        bufs["stem_off"] = np.zeros(int(n) + 1, np.uint32)
+        for k, dt in abi.RECORD_DTYPES.items():
+            bufs[k] = np.zeros(max(int(n), 1), dt)
+
+    def export_records(self, chunk_slots: int = 1 << 20):
+        """The whole table as records: iterates every shard in ranges of
+        chunk_slots slots and yields one dict per range: export_range's arrays
+        (fresh copies) plus "shard" and "info" (that range's rl_export_info)."""
+        bufs = {}
+        for shard in range(self.n_shards()):
+            lo, slots = 0, None
+            while slots is None or lo < slots:
+                rec, info = self.export_range(shard, lo, lo + chunk_slots, bufs)
+                slots = info["shard_slots"]
+                lo += chunk_slots
+                out = {k: v.copy() for k, v in rec.items()}
+                out["shard"], out["info"] = shard, info
+                yield out
+
+    def import_records(self, rec: dict) -> int:
+        """rl_import of export_range's arrays, split at any record boundary into
+        calls of at most max_batch records and max_stem_bytes stem bytes. Returns the calls made."""
+        n = len(rec["ws"])
+        max_n = int(self.cfg.max_batch) or 1 << 20
+        max_b = int(self.cfg.max_stem_bytes) or 128 * max_n
+        off = np.ascontiguousarray(rec["stem_off"], np.uint32)
+        stems = np.ascontiguousarray(rec["stem_bytes"], np.uint8)
+        cols = {k: np.ascontiguousarray(rec[k], dt) for k, dt in abi.RECORD_DTYPES.items()}
+        calls, lo = 0, 0
+        while lo < n:
+            hi = min(n, lo + max_n)
+            if int(off[hi]) - int(off[lo]) > max_b:  # the most records whose stems fit
+                hi = max(lo + 1, int(np.searchsorted(off, int(off[lo]) + max_b, side="right")) - 1)
+            r = abi.RlRecords()
+            r.n = hi - lo
+            sub_off = np.ascontiguousarray(off[lo:hi + 1] - off[lo])
+            sub_stem = stems[int(off[lo]):int(off[hi])]
+            sub = {k: v[lo:hi] for k, v in cols.items()}
+            r.stem_bytes, r.stem_off = abi.ptr(sub_stem), abi.ptr(sub_off)
+            for k, v in sub.items():
+                setattr(r, k, abi.ptr(v))
+            self._check(self.L.rl_import(self.ctx, C.byref(r)))
+            calls += 1
+            lo = hi
+        return calls
+
     def debug_keys(self, pb: PackedBatch) -> List[str]:
         cap = int(pb.arrays["stem_off"][-1]) + 24 * pb.n + 1
         buf = np.zeros(cap, np.uint8)
@@ -330,6 +413,26 @@ class Backend:
         self._check(self.L.rl_debug_decide(self.ctx, n, *[abi.ptr(x) for x in a], abi.ptr(code), abi.ptr(rem),
                                               abi.ptr(reset), abi.ptr(deltas), abi.ptr(lc_set)))
         return code, rem, reset, deltas.reshape(n, abi.RL_NUM_STATS), lc_set
+
+
+def migrate(src: Backend, dst: Backend, chunk_slots: int = 1 << 20) -> dict:
+    """Move every live counter of src into dst (any table_slots, history_entries,
+    hash_seed or shard count): export_records -> import_records. Returns the
+    summed rl_export_info (records, stem_bytes, keys, chains_lost; shard_slots
+    summed over shards; time_floor the source's). Raises RedisError when dst
+    cannot take a record (RL_E_TABLE_FULL / RL_E_ARENA_FULL: its status)."""
+    total = {"shard_slots": 0, "records": 0, "stem_bytes": 0, "keys": 0, "chains_lost": 0, "time_floor": 0}
+    shards = set()
+    for rec in src.export_records(chunk_slots):
+        info = rec["info"]
+        for k in ("records", "stem_bytes", "keys", "chains_lost"):
+            total[k] += info[k]
+        total["time_floor"] = info["time_floor"]
+        if rec["shard"] not in shards:
+            shards.add(rec["shard"])
+            total["shard_slots"] += info["shard_slots"]
+        dst.import_records(rec)
+    return total
 
 
 # rl_status of a device-level failure: the GPU or its runtime, not a request
