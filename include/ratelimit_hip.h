@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RL_ABI_VERSION 7u
+#define RL_ABI_VERSION 8u
 
 /* Status codes. */
 enum rl_status {
@@ -707,6 +707,47 @@ typedef struct rl_export_info {
 int rl_export_range(rl_ctx* ctx, uint32_t shard, uint64_t slot_begin, uint64_t slot_end, rl_records* out,
                     rl_export_info* info);
 int rl_import(rl_ctx* ctx, const rl_records* in);
+
+/* ---- Keyed read of counters (Redis GET + TTL, without counting a hit) --------
+ * rl_lookup answers, per key, what a DoLimit descriptor with that (stem, unit)
+ * and clock would read before its INCRBY. Key i is the Redis key
+ * stem ‖ decimal((now/div)*div) in the store its unit selects under
+ * per_second_split: found / count are what GET returns (the key is not found
+ * once now > expire), expire gives the TTL (expire - now), and lc is the local
+ * over-limit cache entry's expiry where IsOverLimitWithLocalCache would hit
+ * (local cache enabled and now < lc), else 0. A stem counted under several
+ * units shares Redis keys between its unit slots where their windows coincide:
+ * the count is the first record of the window, in unit order, that is live at
+ * now and in the same store; lc any such record's live entry.
+ *
+ * status[i]: RL_OK; RL_E_INVALID for a unit outside 1..4, an empty stem or one
+ * over 65535 bytes; RL_E_TIME exactly where a request with that key and clock
+ * is answered RL_E_TIME (clock outside [0, 2^32 - 172801] or below the sweep
+ * floor; a history chain that breaks before the window is ruled out; a window
+ * further back than the history proves). A failed key's other outputs are 0.
+ *
+ * Strictly read-only: no slot or arena space is claimed, nothing is appended,
+ * no flag is set, and neither rl_table_info nor the local-cache gauges move.
+ * Orders after every submitted batch; synchronous. A multi-shard ctx routes
+ * the keys to their owners on the host and scatters the answers back. Whole-
+ * call failures write nothing: null pointers or bad offsets (stem_off[0] != 0,
+ * decreasing) RL_E_INVALID; n > max_batch or stem bytes > max_stem_bytes
+ * RL_E_CAPACITY; a ctx that joined a communicator RL_E_INVALID. n == 0: RL_OK. */
+typedef struct rl_keys {          /* host memory */
+  uint32_t n, reserved;
+  const uint8_t* stem_bytes;
+  const uint32_t* stem_off;       /* n + 1, stem_off[0] == 0 */
+  const uint8_t* unit;            /* [n] rl_unit */
+  const int64_t* now;             /* [n] the clock the key is read at */
+} rl_keys;
+typedef struct rl_key_state {     /* host memory, same order */
+  uint8_t* status;                /* [n] RL_OK / RL_E_INVALID / RL_E_TIME */
+  uint8_t* found;                 /* [n] 1: the Redis key exists at now */
+  uint32_t* count;                /* [n] its value (0 when !found) */
+  uint32_t* expire;               /* [n] live while now <= expire (0 when !found) */
+  uint32_t* lc;                   /* [n] local over-limit cache entry's expiry if now < lc, else 0 */
+} rl_key_state;
+int rl_lookup(rl_ctx* ctx, const rl_keys* in, rl_key_state* out);
 
 /* Per-stage device timing (HIP events on the batch stream), for benchmarks.
  * rl_profile(ctx, k) with k >= 1 starts accumulating over every k-th batch,

@@ -140,6 +140,21 @@ class RlExportInfo(C.Structure):
 RECORD_DTYPES = {"unit": np.uint8, "flags": np.uint8, "ws": np.uint32, "count": np.uint32,
                  "expire": np.uint32, "lc": np.uint32}
 
+
+class RlKeys(C.Structure):
+    """rl_keys: the (stem, unit, clock) keys of one rl_lookup call."""
+    _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("stem_bytes", P), ("stem_off", P), ("unit", P),
+                ("now", P)]
+
+
+class RlKeyState(C.Structure):
+    """rl_key_state: rl_lookup's answers, one per key."""
+    _fields_ = [("status", P), ("found", P), ("count", P), ("expire", P), ("lc", P)]
+
+
+# the per-key arrays of rl_key_state
+KEY_STATE_DTYPES = {"status": np.uint8, "found": np.uint8, "count": np.uint32, "expire": np.uint32, "lc": np.uint32}
+
 RL_MATCH_NONE, RL_MATCH_UNLIMITED, RL_MATCH_LIMIT = 0, 1, 2
 REQUEST_ARRAYS = ("domain_bytes", "domain_off", "now", "hits", "req_idx", "entry_first", "desc_off", "desc_bytes",
                   "key_len", "value_len", "override_flags", "override_rpu", "override_unit", "override_rule")
@@ -167,7 +182,7 @@ BATCH_DTYPES = {"stem_bytes": np.uint8, "stem_off": np.uint32, "now": np.int64, 
                 "rule_id": np.uint32}
 RESULT_DTYPES = {"code": np.uint8, "limit_remaining": np.uint32, "reset_s": np.uint32, "stats": np.uint64,
                  "status": np.uint8}
-ABI_VERSION = 7
+ABI_VERSION = 8
 RL_COMM_ID_BYTES = 128  # include/ratelimit_hip.h
 RL_ROUTED_INFLIGHT = 6  # include/ratelimit_hip.h (routed batches in flight: the input-reuse distance)
 RL_ROUTED_LAG = 3  # include/ratelimit_hip.h (calls between a routed batch's partition and its owner pipeline)

@@ -820,6 +820,64 @@ int rl_import(rl_ctx* c, const rl_records* in) {
   return RL_OK;
 }
 
+int rl_lookup(rl_ctx* c, const rl_keys* in, rl_key_state* out) {
+  if (!c || !in || !out) return fail(c, RL_E_INVALID, "gpu: null argument");
+  if (c->comm) return fail(c, RL_E_INVALID, "gpu: rl_lookup is not for a ctx that joined a communicator");
+  if (const int src = settle_local(c)) return src;
+  if (c->n == 1) return eng_lookup(c->e[0], in, out);
+  // the whole call is checked first (a bad call writes nothing), then the keys
+  // go to their owners, routed on the host like rl_import's records, and the
+  // answers come back in the caller's order
+  if (const int rc = from_engine(c, c->e[0], eng_lookup_check(c->e[0], in, out))) return rc;
+  const uint32_t N = c->n;
+  std::vector<std::vector<uint32_t>> idx(N);
+  for (uint32_t i = 0; i < in->n; i++) {
+    const uint32_t a = in->stem_off[i], b = in->stem_off[i + 1];
+    idx[owner_of_host(hash_stem_host(c->e[0]->hk, in->stem_bytes + a, b - a), N)].push_back(i);
+  }
+  struct Sub {
+    std::vector<uint8_t> stems, unit, status, found;
+    std::vector<uint32_t> off{0}, count, expire, lc;
+    std::vector<int64_t> now;
+  };
+  std::vector<Sub> sub(N);
+  for (uint32_t j = 0; j < N; j++) {
+    if (idx[j].empty()) continue;
+    Sub& s = sub[j];
+    for (uint32_t i : idx[j]) {
+      s.stems.insert(s.stems.end(), in->stem_bytes + in->stem_off[i], in->stem_bytes + in->stem_off[i + 1]);
+      s.off.push_back((uint32_t)s.stems.size());
+      s.unit.push_back(in->unit[i]);
+      s.now.push_back(in->now[i]);
+    }
+    const size_t m = idx[j].size();
+    s.stems.push_back(0);  // (never null, even when every stem is empty)
+    s.status.resize(m);
+    s.found.resize(m);
+    s.count.resize(m);
+    s.expire.resize(m);
+    s.lc.resize(m);
+    rl_keys k{};
+    k.n = (uint32_t)m;
+    k.stem_bytes = s.stems.data();
+    k.stem_off = s.off.data();
+    k.unit = s.unit.data();
+    k.now = s.now.data();
+    rl_key_state o{s.status.data(), s.found.data(), s.count.data(), s.expire.data(), s.lc.data()};
+    if (const int rc = from_engine(c, c->e[j], eng_lookup(c->e[j], &k, &o))) return rc;  // (nothing scattered yet)
+  }
+  for (uint32_t j = 0; j < N; j++)
+    for (size_t x = 0; x < idx[j].size(); x++) {
+      const uint32_t i = idx[j][x];
+      out->status[i] = sub[j].status[x];
+      out->found[i] = sub[j].found[x];
+      out->count[i] = sub[j].count[x];
+      out->expire[i] = sub[j].expire[x];
+      out->lc[i] = sub[j].lc[x];
+    }
+  return RL_OK;
+}
+
 int rl_config_load(rl_ctx* c, const rl_config_tree* t) {
   if (!c) return fail(c, RL_E_INVALID, "gpu: null ctx");
   if (c->n > 1 && t && t->nodes)  // (the shards' own check allows their n x max_rules rows)

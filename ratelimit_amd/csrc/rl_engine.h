@@ -225,6 +225,11 @@ int eng_export_range(Engine* c, uint64_t slot_begin, uint64_t slot_end, rl_recor
 // eng_import runs them too.
 int eng_import_check(Engine* c, const rl_records* in);
 int eng_import(Engine* c, const rl_records* in);
+// rl_lookup's whole-call checks against this engine's limits (host only;
+// eng_lookup runs them too), and the lookup on this engine's table. The call
+// reuses the staging of the host-buffer entry points: nothing is allocated.
+int eng_lookup_check(Engine* c, const rl_keys* in, const rl_key_state* out);
+int eng_lookup(Engine* c, const rl_keys* in, rl_key_state* out);
 
 // Owner side of a routed batch, pipelined on the engine's streams like
 // eng_do_limit_async: unpack the n received wire records (chunks of n_src

@@ -1997,4 +1997,49 @@ int eng_import(Engine* c, const rl_records* in) {
   return map_err(c, e);
 }
 
+int eng_lookup_check(Engine* c, const rl_keys* in, const rl_key_state* out) {
+  if (!c || !in || !out) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  const uint32_t n = in->n;
+  if (n > c->cfg.max_batch) return set_err(c, RL_E_CAPACITY, "gpu: lookup exceeds configured max_batch");
+  if (!n) return RL_OK;
+  if (!in->stem_bytes || !in->stem_off || !in->unit || !in->now)
+    return set_err(c, RL_E_INVALID, "gpu: null rl_keys array");
+  if (!out->status || !out->found || !out->count || !out->expire || !out->lc)
+    return set_err(c, RL_E_INVALID, "gpu: null rl_key_state array");
+  if (in->stem_off[0] != 0) return set_err(c, RL_E_INVALID, "gpu: lookup stem offsets must start at 0");
+  for (uint32_t i = 0; i < n; i++)  // (an empty or over-long stem is that key's own status)
+    if (in->stem_off[i + 1] < in->stem_off[i])
+      return set_err(c, RL_E_INVALID, "gpu: lookup key " + std::to_string(i) + ": stem offsets decrease");
+  if (in->stem_off[n] > c->cfg.max_stem_bytes)
+    return set_err(c, RL_E_CAPACITY, "gpu: lookup exceeds configured max_stem_bytes");
+  return RL_OK;
+}
+
+int eng_lookup(Engine* c, const rl_keys* in, rl_key_state* out) {
+  if (const int rc = eng_lookup_check(c, in, out)) return rc;
+  const uint32_t n = in->n;
+  if (!n) return RL_OK;
+  const uint32_t nb = in->stem_off[n];
+  std::vector<uint32_t> now32(n);  // the clocks as the table keeps them
+  for (uint32_t i = 0; i < n; i++)
+    now32[i] = in->now[i] < 0 || in->now[i] > (int64_t)NOW_MAX ? LOOKUP_NOW_BAD : (uint32_t)in->now[i];
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream;
+  HIPCHK(c, after_batches(c, st));  // (the staging below is the synchronous entry points': free by then)
+  if (nb) HIPCHK(c, hipMemcpyAsync(c->d_stem, in->stem_bytes, nb, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->d_off, in->stem_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->d_unit, in->unit, n, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(c->d_req, now32.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+  const LookupDev q{n, c->d_off, c->d_unit, c->d_req, c->d_status, c->d_code, c->d_rem, c->d_reset, c->d_limit};
+  launch_lookup(table_view(c), c->hk, params(c), c->s[0].time_floor, c->d_stem, nb, q, st);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out->status, q.status, n, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->found, q.found, n, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->count, q.count, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->expire, q.expire, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out->lc, q.lc, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));  // (now32 lives until here)
+  return RL_OK;
+}
+
 }  // namespace rl

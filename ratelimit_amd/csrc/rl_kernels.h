@@ -411,6 +411,23 @@ static_assert(sizeof(ImportRec) == 32, "ImportRec is two dwordx4");
 void launch_import(const TableDev& t, const HashKey& hk, const uint8_t* stem, uint32_t stem_total, const ImportRec* rec,
                    const uint32_t* gstart, const unsigned long long* ghash, uint32_t ng, unsigned long long* epoch,
                    uint32_t* err, hipStream_t st);
+// ---- keyed read of counters (rl_lookup): one lane per key, read-only ----
+// Device staging of one lookup call (the engine's own). now: the key's clock as
+// the table keeps it (LOOKUP_NOW_BAD: outside [0, NOW_MAX] on the host).
+constexpr uint32_t LOOKUP_NOW_BAD = 0xFFFFFFFFu;  // (> NOW_MAX)
+struct LookupDev {
+  uint32_t n;
+  const uint32_t* off;  // n + 1 stem offsets
+  const uint8_t* unit;
+  const uint32_t* now;
+  uint8_t *status, *found;
+  uint32_t *count, *expire, *lc;
+};
+// Stems in `stem` (16-B aligned, readable to the next 16-B boundary past
+// stem_total; off[n] <= stem_total). Writes the five output arrays of every
+// key and nothing else: no slot, no arena space, no log entry, no counter.
+void launch_lookup(const TableDev& t, const HashKey& hk, const Params& P, const int64_t* time_floor,
+                   const uint8_t* stem, uint32_t stem_total, const LookupDev& q, hipStream_t st);
 // Built with RL_LOG_TEAR (rl_debug_log_tear's hook in the history log's lookups)?
 bool log_tear_hook();
 void launch_debug_keys(const BatchDev& b, uint8_t* out, uint32_t* klen, hipStream_t st);

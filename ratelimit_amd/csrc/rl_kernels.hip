@@ -22,7 +22,8 @@
 //                 first with the local cache on)
 //   k_finish      packed results -> code / limit_remaining / reset_s, and the
 //                 striped per-block stats -> rl_result.stats
-// plus k_sweep (epoch sweep = Redis EXPIRE), k_table_info, debug kernels.
+// plus k_sweep (epoch sweep = Redis EXPIRE), k_table_info, the export / import
+// kernels, k_lookup (a key's counter read without a hit), debug kernels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstdlib>
@@ -5392,6 +5393,155 @@ __global__ __launch_bounds__(256) void k_import(const TableDev t, const BatchDev
 }
 
 // ===========================================================================
+// Keyed lookup (rl_lookup): what a DoLimit descriptor with this (stem, unit)
+// and clock would read before its INCRBY — Redis GET + TTL of the key
+// stem ‖ windowStart and the local over-limit cache's Get — without the hit.
+// One lane per key: hash the stem (from the 64-B head key_of loads anyway, the
+// rest through the StemRef), probe read-only from the home slot (whole 64-B
+// sectors; tag, then unit and full stem; over tombstones, to the first empty
+// slot or max_probe), resolve the window on the slot (cur, absent above cur,
+// the history chain below it). A stem whose slot is flagged SLOT_EXACT, or that
+// has no slot of this unit (the batch path would insert one and look for the
+// others), is read through every unit slot it has: general_step's read rule,
+// restated — the count is the first record of the window, in unit order, live
+// at `now` in the same store; the local-cache entry any record's. RL_E_TIME
+// where the batch path says so (simple_pick / gen_rec), never a guess.
+// Nothing is written but the output arrays: the chain walk is log_find without
+// its history_lost count (and without the re-read: the call orders after every
+// batch, nothing writes meanwhile).
+// ===========================================================================
+__device__ inline int lookup_find(const TableDev& t, uint32_t head, uint32_t si, uint32_t tag, uint32_t cur_ws,
+                                  uint32_t w, Win* out) {
+  uint32_t ptr = head, tprev = cur_ws, saved = LOG_NONE, power = 1, lam = 0;
+  for (uint32_t hops = 0; ptr != LOG_NONE; hops++) {
+    const uint32_t pos = ptr & LOG_POS_MASK;
+    if (hops == LOG_MAX_HOPS || pos >= t.log_cap || ptr == saved) return -1;
+    if (++lam == power) {
+      saved = ptr;
+      power <<= 1;
+      lam = 0;
+    }
+    const uint4* e = reinterpret_cast<const uint4*>(&t.log[(size_t)(ptr >> LOG_POS_BITS) * t.log_cap + pos]);
+    const uint4 a = e[0], b = e[1];
+    if (a.x != si || a.y != tag || a.w > tprev) return -1;  // overwritten (owner, order) or being written
+    if (b.x == w) {
+      *out = Win{b.x, b.y, b.z, b.w};
+      return 1;
+    }
+    if (a.w <= w) return 0;  // every older entry holds a window below its t_app <= w
+    tprev = a.w;
+    ptr = a.z;
+  }
+  return 0;
+}
+
+// hash_stem over a Key: the zero-padded head's dwords are in registers.
+__device__ inline uint64_t hash_key(const HashKey& hk, const Key& key) {
+  const uint32_t len = key.len;
+  StemHasher hs(hk, len);
+  uint64_t tail = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < KEY_HEAD / 8; k++) {
+    const uint64_t m = (uint64_t)key_dw(key, 2 * k) | ((uint64_t)key_dw(key, 2 * k + 1) << 32);
+    if (8 * k + 8 <= len) hs.word(m);
+    else if (8 * k < len) tail = m;  // (the head is zero above the stem)
+  }
+  if (len > KEY_HEAD) {
+    uint32_t i = KEY_HEAD;
+    for (; i + 8 <= len; i += 8) hs.word((uint64_t)key.st.word(i >> 2) | ((uint64_t)key.st.word((i >> 2) + 1) << 32));
+    if (i < len)
+      tail = ((uint64_t)key.st.word(i >> 2) | ((uint64_t)key.st.word((i >> 2) + 1) << 32)) &
+             ((1ull << ((len - i) * 8)) - 1);
+  }
+  return hs.finish(tail, hk.hi_bits);
+}
+
+__global__ __launch_bounds__(256) void k_lookup(const TableDev t, const BatchDev b, const Params P,
+                                                const int64_t* __restrict__ time_floor, const LookupDev q) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= q.n) return;
+  const uint32_t s0 = q.off[i], s1 = q.off[i + 1], u = q.unit[i], now = q.now[i];
+  uint32_t status = RL_OK, found = 0, count = 0, expire = 0, lc = 0;
+  if (s1 <= s0 || s1 - s0 > 65535u || s1 > b.stem_total || u < 1 || u > 4) {
+    status = RL_E_INVALID;
+  } else if (now > NOW_MAX || (int64_t)now < *time_floor) {
+    status = RL_E_TIME;
+  } else {
+    Rec r0{};
+    r0.off = s0;
+    r0.lu = s1 - s0;
+    const Key key = key_of(b, r0);
+    uint64_t hs = hash_key(b.hk, key);
+    if ((uint32_t)(hs >> 32) == KEY_DUP) hs = ((uint64_t)(KEY_DUP - 1u) << 32) | (uint32_t)hs;  // (as k_prepare homes it)
+    const uint32_t tag = slot_tag(hs, u);
+    // this unit's slot
+    SlotImg im;
+    uint64_t j = hs >> t.shift;
+    bool hit = false;
+    for (uint32_t p = 0; p < t.max_probe; p++, j = (j + 1) & t.mask) {
+      load_img_lo(&t.slots[j], im);
+      const uint32_t tg = im.tag();
+      if (tg == TAG_EMPTY) break;
+      if (tg == tag && im.unit() == u && img_key_equal(im, key, t.arena)) {  // (a 32-bit tag is a filter)
+        hit = true;
+        break;
+      }
+    }
+    int64_t sidx[4];
+    Win c[4];
+    uint32_t chain[4], present;
+    if (hit && !(im.flags() & SLOT_EXACT)) {  // the stem has this unit only: no other slot is looked at
+      present = 1u << (u - 1);
+#pragma unroll
+      for (uint32_t k = 0; k < 4; k++) {  // (all four, so that no store is indexed by u: only entry u - 1 is read)
+        sidx[k] = (int64_t)j;
+        c[k] = im.cur();
+        chain[k] = im.ring();
+      }
+    } else {
+      present = find_unit_slots(t, hs, key, sidx, c, chain) & 0xFu;
+    }
+    const uint32_t w = now - now % div_of(u);
+    const bool cls = P.per_second && u == RL_UNIT_SECOND;
+    bool lost = false, vf = false;
+    uint32_t lcw = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+      if (!((present >> k) & 1)) continue;
+      const uint32_t d = div_of(k + 1);
+      Win R = c[k];
+      if (R.ws != w) {
+        if (R.ws == WS_INVALID || w > R.ws || w % d) continue;  // (unit k's keys are multiples of its div)
+        const int f =
+            chain[k] == LOG_NONE ? 0 : lookup_find(t, chain[k], (uint32_t)sidx[k], slot_tag(hs, k + 1), c[k].ws, w, &R);
+        if (f <= 0) {
+          if (f < 0 ? !hist_dead(now, w, d) : !hist_absent_ok(t, now, w, c[k].ws, d)) lost = true;
+          continue;
+        }
+      }
+      lcw = R.lc > lcw ? R.lc : lcw;
+      if ((P.per_second && k == 0) == cls && !vf && now <= R.expire) {
+        vf = true;
+        count = R.count;
+        expire = R.expire;
+      }
+    }
+    if (lost) {  // a record of w the history may have dropped while it could be live
+      status = RL_E_TIME;
+      count = expire = 0;
+    } else {
+      found = vf ? 1u : 0u;
+      lc = (P.lc_en && now < lcw) ? lcw : 0u;
+    }
+  }
+  q.status[i] = (uint8_t)status;
+  q.found[i] = (uint8_t)found;
+  q.count[i] = count;
+  q.expire[i] = expire;
+  q.lc[i] = lc;
+}
+
+// ===========================================================================
 // Diagnostics
 // ===========================================================================
 // Full Redis key stem ‖ strconv.FormatInt((now/div)*div, 10) into a padded
@@ -5619,6 +5769,16 @@ void launch_import(const TableDev& t, const HashKey& hk, const uint8_t* stem, ui
   b.stem = stem;
   b.stem_cap = b.stem_total = stem_total;
   k_import<<<cdiv(ng, 256), 256, 0, st>>>(tv, b, rec, gstart, ghash, ng, err);
+}
+
+void launch_lookup(const TableDev& t, const HashKey& hk, const Params& P, const int64_t* time_floor,
+                   const uint8_t* stem, uint32_t stem_total, const LookupDev& q, hipStream_t st) {
+  if (!q.n) return;
+  BatchDev b{};
+  b.hk = hk;
+  b.stem = stem;
+  b.stem_cap = b.stem_total = stem_total;
+  k_lookup<<<cdiv(q.n, 256), 256, 0, st>>>(t, b, P, time_floor, q);
 }
 
 bool log_tear_hook() { return RL_LOG_TEAR != 0; }

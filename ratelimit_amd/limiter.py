@@ -17,7 +17,7 @@ is the batcher's entry point: many in-flight calls, one GPU launch sequence.
 """
 import ctypes as C
 import time
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -30,7 +30,16 @@ from .types import OK, DescriptorStatus, Limit  # noqa: F401  (re-exported data 
 STAGES = ("prepare", "sort", "segment", "table", "finish")
 PROFILE_FIELDS = STAGES + ("table_kernel",)  # + k_table's own run time (device clock)
 
-__all__ = ["GpuRateLimitCache", "GpuRateLimitService", "RedisError", "TimeSource", "migrate"]
+__all__ = ["GpuRateLimitCache", "GpuRateLimitService", "KeyState", "RedisError", "TimeSource", "migrate"]
+
+
+class KeyState(NamedTuple):
+    """One Redis key as GpuRateLimitCache.peek reads it: GET's value (0 when the
+    key does not exist), its TTL in seconds (None: no such key) and whether the
+    local over-limit cache holds it."""
+    count: int
+    ttl_s: Optional[int]
+    over_limit_cached: bool
 
 
 class TimeSource:
@@ -392,6 +401,48 @@ class Backend:
             lo = hi
         return calls
 
+    # ---- keyed read of counters (Redis GET + TTL, no hit counted)
+    def lookup(self, stems: Sequence[bytes], units, nows) -> dict:
+        """rl_lookup of the keys (stems[i], units[i]) read at the clocks nows[i], in
+        calls of at most max_batch keys and max_stem_bytes stem bytes. Returns
+        numpy arrays status / found / count / expire / lc, one entry per key
+        (abi.KEY_STATE_DTYPES); a key's failure is its status, a failed call raises."""
+        n = len(stems)
+        max_n = int(self.cfg.max_batch) or 1 << 20
+        max_b = int(self.cfg.max_stem_bytes) or 128 * max_n
+        unit = np.ascontiguousarray(units, np.uint8).reshape(-1)
+        now = np.ascontiguousarray(nows, np.int64).reshape(-1)
+        if len(unit) != n or len(now) != n:
+            raise ValueError("lookup: stems, units and nows must have one entry per key")
+        off = np.zeros(n + 1, np.int64)
+        if n:
+            off[1:] = np.cumsum([len(s) for s in stems], dtype=np.int64)
+        blob = np.frombuffer(b"".join(stems), np.uint8) if n and off[n] else np.zeros(0, np.uint8)
+        out = {k: np.zeros(n, dt) for k, dt in abi.KEY_STATE_DTYPES.items()}
+        lo = 0
+        while lo < n:
+            hi = min(n, lo + max_n)
+            if int(off[hi]) - int(off[lo]) > max_b:  # the most keys whose stems fit (one alone: the call says so)
+                hi = max(lo + 1, int(np.searchsorted(off, int(off[lo]) + max_b, side="right")) - 1)
+            sub_off = np.ascontiguousarray(off[lo:hi + 1] - off[lo], np.uint32)
+            sub_stem = np.ascontiguousarray(blob[int(off[lo]):int(off[hi])])
+            if sub_stem.size == 0:
+                sub_stem = np.zeros(1, np.uint8)
+            k = abi.RlKeys()
+            k.n = hi - lo
+            k.stem_bytes, k.stem_off = abi.ptr(sub_stem), abi.ptr(sub_off)
+            sub_unit, sub_now = unit[lo:hi], now[lo:hi]
+            k.unit, k.now = abi.ptr(sub_unit), abi.ptr(sub_now)
+            res = {f: np.zeros(hi - lo, dt) for f, dt in abi.KEY_STATE_DTYPES.items()}
+            s = abi.RlKeyState()
+            for f, v in res.items():
+                setattr(s, f, abi.ptr(v))
+            self._check(self.L.rl_lookup(self.ctx, C.byref(k), C.byref(s)))
+            for f, v in res.items():
+                out[f][lo:hi] = v
+            lo = hi
+        return out
+
     def debug_keys(self, pb: PackedBatch) -> List[str]:
         cap = int(pb.arrays["stem_off"][-1]) + 24 * pb.n + 1
         buf = np.zeros(cap, np.uint8)
@@ -524,6 +575,36 @@ class GpuRateLimitCache:
                 if v:
                     setattr(stats, f, getattr(stats, f) + int(v))
         return outs
+
+    def peek(self, request, limits, now: Optional[int] = None) -> list:
+        """What do_limit would read for this request at `now` (default: the time
+        source's), without counting a hit: per descriptor None for a nil limit,
+        else KeyState(count, ttl_s, over_limit_cached) of its Redis key — the same
+        stems do_limit builds (prefix ‖ domain ‖ entries). Raises RedisError when
+        a key cannot be answered (its rl_status)."""
+        from .packing import stem_of
+        if len(request.descriptors) != len(limits):
+            raise AssertionError("len(descriptors) != len(limits)")  # base_limiter.go:47
+        now = self.time_source.unix_now() if now is None else int(now)
+        where, stems, units = [], [], []
+        for i, (d, lim) in enumerate(zip(request.descriptors, limits)):
+            if lim is None:
+                continue
+            where.append(i)
+            stems.append(stem_of(self.prefix, request.domain, d.entries))
+            units.append(int(lim.limit.unit))
+        out = [None] * len(limits)
+        if not stems:
+            return out
+        res = self.backend.lookup(stems, units, [now] * len(stems))
+        for j, i in enumerate(where):
+            st = int(res["status"][j])
+            if st:
+                raise RedisError("gpu: key lookup failed [%s]" % abi.STATUS_NAMES.get(st, st), st)
+            found = bool(res["found"][j])
+            out[i] = KeyState(int(res["count"][j]), int(res["expire"][j]) - now if found else None,
+                              bool(res["lc"][j]))
+        return out
 
     def flush(self):
         """Flush(): nothing is asynchronous on the host path."""
