@@ -21,9 +21,15 @@ import (
 // must not be handed Go memory that holds Go pointers, which the
 // rl_request_batch struct would be), grown on demand. rl_do_limit_requests is
 // synchronous: the outputs are final when DoLimitRequests returns.
+//
+// DoLimitRequestsVerdict also answers the rest of shouldRateLimitWorker per
+// request on the GPU (src/service/ratelimit.go:163-209): OverallCode, the
+// minimumDescriptor's values behind the RateLimit-* headers and global shadow
+// mode (rl_do_limit_requests_verdict), into the per-request arrays below.
 type RequestBatch struct {
-	In  C.rl_request_batch
-	Out C.rl_request_result
+	In      C.rl_request_batch
+	Out     C.rl_request_result
+	Verdict C.rl_request_verdict
 
 	bufs []pinnedBuf
 
@@ -37,6 +43,15 @@ type RequestBatch struct {
 	Unit      []uint8
 	Stats     []uint64
 	NDesc     int
+
+	// outputs per request (DoLimitRequestsVerdict)
+	OverallCode     []uint8  // RateLimitResponse.OverallCode
+	VerdictFlags    []uint8  // VerdictOverLimit | VerdictGlobalShadow
+	MinDescriptor   []uint32 // batch index of the header descriptor, NoDescriptor for none
+	HeaderLimit     []uint32
+	HeaderRemaining []uint32
+	HeaderReset     []uint32
+	globalShadow    []uint64 // [1]
 }
 
 // pinnedBuf is one growable page-locked array.
@@ -79,6 +94,13 @@ const (
 	rbRPU
 	rbUnit
 	rbStats
+	rbOverall
+	rbVFlags
+	rbMinDesc
+	rbHdrLimit
+	rbHdrRem
+	rbHdrReset
+	rbShadow
 	rbCount
 )
 
@@ -201,6 +223,21 @@ func (b *RequestBatch) Pack(reqs []*pb.RateLimitRequest, nows []int64,
 	b.Out.requests_per_unit = (*C.uint32_t)(b.bufs[rbRPU].p)
 	b.Out.unit = (*C.uint8_t)(b.bufs[rbUnit].p)
 	b.Out.stats = (*C.uint64_t)(b.bufs[rbStats].p)
+	// per request
+	b.OverallCode = bytesAt(b.bufs[rbOverall].ensure(nq+1), nq)
+	b.VerdictFlags = bytesAt(b.bufs[rbVFlags].ensure(nq+1), nq)
+	b.MinDescriptor = u32At(b.bufs[rbMinDesc].ensure(4*nq+4), nq)
+	b.HeaderLimit = u32At(b.bufs[rbHdrLimit].ensure(4*nq+4), nq)
+	b.HeaderRemaining = u32At(b.bufs[rbHdrRem].ensure(4*nq+4), nq)
+	b.HeaderReset = u32At(b.bufs[rbHdrReset].ensure(4*nq+4), nq)
+	b.globalShadow = u64At(b.bufs[rbShadow].ensure(8), 1)
+	b.Verdict.overall_code = (*C.uint8_t)(b.bufs[rbOverall].p)
+	b.Verdict.flags = (*C.uint8_t)(b.bufs[rbVFlags].p)
+	b.Verdict.min_descriptor = (*C.uint32_t)(b.bufs[rbMinDesc].p)
+	b.Verdict.header_limit = (*C.uint32_t)(b.bufs[rbHdrLimit].p)
+	b.Verdict.header_remaining = (*C.uint32_t)(b.bufs[rbHdrRem].p)
+	b.Verdict.header_reset_s = (*C.uint32_t)(b.bufs[rbHdrReset].p)
+	b.Verdict.global_shadow = (*C.uint64_t)(b.bufs[rbShadow].p)
 }
 
 // Match results (rl_match).
@@ -213,4 +250,34 @@ const (
 // DoLimitRequests runs a packed RequestBatch (synchronous; not on a routed ctx).
 func (c *Ctx) DoLimitRequests(b *RequestBatch) error {
 	return c.err(C.rl_do_limit_requests(c.c, &b.In, &b.Out))
+}
+
+// Verdict flags (rl_request_verdict.flags) and the "no header descriptor" index.
+const (
+	VerdictOverLimit    = uint8(C.RL_VERDICT_OVER_LIMIT)
+	VerdictGlobalShadow = uint8(C.RL_VERDICT_GLOBAL_SHADOW)
+	NoDescriptor        = uint32(C.RL_NO_DESCRIPTOR)
+)
+
+// DoLimitRequestsVerdict is DoLimitRequests plus the per-request verdict:
+// b.OverallCode[q] is the response's OverallCode; where b.MinDescriptor[q] is
+// not NoDescriptor, b.HeaderLimit / HeaderRemaining / HeaderReset [q] are the
+// values of ResponseHeadersToAdd (ratelimit.go:194-201, 213-237). globalShadow
+// is settings SHADOW_MODE (:203-207); the returned count is what the caller
+// adds to stats.GlobalShadowMode. perDescriptor false: the per-descriptor
+// arrays (b.Code ... b.Unit) are not copied back, only b.Stats and the
+// per-request arrays are.
+func (c *Ctx) DoLimitRequestsVerdict(b *RequestBatch, globalShadow bool, perDescriptor bool) (uint64, error) {
+	opts := C.uint32_t(0)
+	if globalShadow {
+		opts = C.RL_VERDICT_OPT_GLOBAL_SHADOW
+	}
+	out := b.Out
+	if !perDescriptor {
+		out = C.rl_request_result{stats: b.Out.stats}
+	}
+	if err := c.err(C.rl_do_limit_requests_verdict(c.c, &b.In, &out, opts, &b.Verdict)); err != nil {
+		return 0, err
+	}
+	return b.globalShadow[0], nil
 }

@@ -29,6 +29,9 @@
 extern "C" {
 #endif
 
+/* Stays 8 with rl_do_limit_requests_verdict / rl_debug_verdict and
+ * rl_request_verdict: they only add symbols and types; no existing struct,
+ * signature or behaviour changed. */
 #define RL_ABI_VERSION 8u
 
 /* Status codes. */
@@ -595,6 +598,59 @@ typedef struct rl_request_result {
  * go through the shards like a device batch (every owner answers its keys);
  * not on a ctx that joined a communicator. */
 int rl_do_limit_requests(rl_ctx* ctx, const rl_request_batch* in, rl_request_result* out);
+
+/* The rest of shouldRateLimitWorker per request (ratelimit.go:163-209, with
+ * customHeadersEnabled): RateLimitResponse.OverallCode, the descriptor
+ * "closest to its limit" whose values the RateLimit-Limit / -Remaining / -Reset
+ * headers carry (minimumDescriptor, :165-176 and :185-190; the header values,
+ * :194-201 and :213-237), and global SHADOW_MODE with its global_shadow_mode
+ * counter (:203-207). Request q's descriptors are the d with req_idx[d] == q
+ * (contiguous, in order):
+ *  - some d has match == RL_MATCH_LIMIT and code == RL_CODE_OVER_LIMIT:
+ *    finalCode OVER_LIMIT, minimumDescriptor = the last such d;
+ *  - otherwise finalCode OK and minimumDescriptor = the first d with match ==
+ *    RL_MATCH_LIMIT and the smallest limit_remaining (the reference compares
+ *    with a strict <, starting from MaxUint32: a remaining of MaxUint32 is
+ *    never chosen); none: RL_NO_DESCRIPTOR and header values 0. Unlimited and
+ *    unmatched descriptors have no CurrentLimit and are never chosen.
+ * header_reset_s is that descriptor's own reset_s: the reference reads its
+ * header clock a moment after DoLimit's, this backend has one clock per request.
+ * With RL_VERDICT_OPT_GLOBAL_SHADOW an OVER_LIMIT finalCode is answered OK,
+ * flagged RL_VERDICT_OVER_LIMIT | RL_VERDICT_GLOBAL_SHADOW and counted in
+ * *global_shadow; the headers stay as computed. A request without descriptors:
+ * OK, RL_NO_DESCRIPTOR, flags 0. */
+#define RL_NO_DESCRIPTOR 0xFFFFFFFFu
+#define RL_VERDICT_OVER_LIMIT    0x1u  /* finalCode was OVER_LIMIT before global shadow mode */
+#define RL_VERDICT_GLOBAL_SHADOW 0x2u  /* ... and global shadow mode turned it into OK */
+#define RL_VERDICT_OPT_GLOBAL_SHADOW 0x1u  /* opts: settings SHADOW_MODE (ratelimit.go:203) */
+
+typedef struct rl_request_verdict {   /* host memory, one entry per request */
+  uint8_t*  overall_code;      /* [n_requests] rl_code: RateLimitResponse.OverallCode */
+  uint8_t*  flags;             /* [n_requests] RL_VERDICT_* (may be NULL) */
+  uint32_t* min_descriptor;    /* [n_requests] batch index of minimumDescriptor, RL_NO_DESCRIPTOR if nil (may be NULL) */
+  uint32_t* header_limit;      /* [n_requests] its CurrentLimit.RequestsPerUnit (may be NULL) */
+  uint32_t* header_remaining;  /* [n_requests] its LimitRemaining (may be NULL) */
+  uint32_t* header_reset_s;    /* [n_requests] its DurationUntilReset seconds (may be NULL) */
+  uint64_t* global_shadow;     /* [1] requests flagged RL_VERDICT_GLOBAL_SHADOW: stats.GlobalShadowMode.Add (may be NULL) */
+} rl_request_verdict;
+
+/* rl_do_limit_requests plus the verdict (same table effects, stats and
+ * per-descriptor answers; synchronous; multi-shard: the verdict runs on shard
+ * 0 after the expansion; not on a ctx that joined a communicator). out may be
+ * NULL, as may any array in it: those are not copied back, so that with
+ * out == NULL only per-request bytes return to the host. verdict and
+ * verdict->overall_code are required (RL_E_INVALID). A batch that fails writes
+ * nothing to *verdict's arrays. */
+int rl_do_limit_requests_verdict(rl_ctx* ctx, const rl_request_batch* in, rl_request_result* out,
+                                 uint32_t opts, rl_request_verdict* verdict);
+/* Diagnostics (parity tests, like rl_debug_decide): the device verdict alone on
+ * explicit per-descriptor answers in host arrays. req_idx must be non-decreasing
+ * and < n_requests (RL_E_INVALID); n_descriptors <= max_batch and n_requests <=
+ * max_requests (RL_E_CAPACITY). */
+int rl_debug_verdict(rl_ctx* ctx, uint32_t n_requests, uint32_t n_descriptors, const uint32_t* req_idx,
+                     const uint8_t* match, const uint8_t* code, const uint32_t* limit_remaining,
+                     const uint32_t* reset_s, const uint32_t* requests_per_unit, uint32_t opts,
+                     rl_request_verdict* verdict);
 
 /* ---- Host packer -------------------------------------
  * Serialized envoy.service.ratelimit.v3.RateLimitRequest messages (the gRPC

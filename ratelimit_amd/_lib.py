@@ -21,7 +21,8 @@ EXPORTS = ["rl_abi_version", "rl_create", "rl_destroy", "rl_last_error", "rl_do_
            "rl_packer_create", "rl_packer_destroy", "rl_packer_pack", "rl_packer_rules", "rl_packer_rule_key",
            "rl_packer_last_error", "rl_comm_unique_id", "rl_comm_loopback_id", "rl_comm_init", "rl_do_limit_routed_async",
            "rl_do_limit_host_async", "rl_do_limit_compact_async", "rl_do_limit_prefixed_async", "rl_batch_progress",
-           "rl_debug_log_tear", "rl_export_range", "rl_import", "rl_lookup"]
+           "rl_debug_log_tear", "rl_export_range", "rl_import", "rl_lookup", "rl_do_limit_requests_verdict",
+           "rl_debug_verdict"]
 
 _libs = {}
 
@@ -117,6 +118,12 @@ def load(path):
         L.rl_import.argtypes = [C.c_void_p, C.POINTER(abi.RlRecords)]
     if hasattr(L, "rl_lookup"):
         L.rl_lookup.argtypes = [C.c_void_p, C.POINTER(abi.RlKeys), C.POINTER(abi.RlKeyState)]
+    if hasattr(L, "rl_do_limit_requests_verdict"):
+        L.rl_do_limit_requests_verdict.argtypes = [C.c_void_p, C.POINTER(abi.RlRequestBatch),
+                                                   C.POINTER(abi.RlRequestResult), C.c_uint32,
+                                                   C.POINTER(abi.RlRequestVerdict)]
+        L.rl_debug_verdict.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [
+            C.c_uint32, C.POINTER(abi.RlRequestVerdict)]
     if L.rl_abi_version() != abi.ABI_VERSION:
         raise RuntimeError("libratelimit_hip.so ABI mismatch")
     _libs[path] = L

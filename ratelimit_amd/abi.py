@@ -117,6 +117,22 @@ class RlRequestResult(C.Structure):
                 ("requests_per_unit", P), ("unit", P), ("stats", P)]
 
 
+RL_NO_DESCRIPTOR = 0xFFFFFFFF
+RL_VERDICT_OVER_LIMIT, RL_VERDICT_GLOBAL_SHADOW = 1, 2  # rl_request_verdict.flags
+RL_VERDICT_OPT_GLOBAL_SHADOW = 1  # rl_do_limit_requests_verdict opts
+
+
+class RlRequestVerdict(C.Structure):
+    """rl_request_verdict: per request, the overall code and the header descriptor's values."""
+    _fields_ = [("overall_code", P), ("flags", P), ("min_descriptor", P), ("header_limit", P),
+                ("header_remaining", P), ("header_reset_s", P), ("global_shadow", P)]
+
+
+# the per-request arrays of rl_request_verdict (global_shadow apart: one uint64)
+REQUEST_VERDICT_DTYPES = {"overall_code": np.uint8, "flags": np.uint8, "min_descriptor": np.uint32,
+                          "header_limit": np.uint32, "header_remaining": np.uint32, "header_reset_s": np.uint32}
+
+
 class RlLocalCacheInfo(C.Structure):
     _fields_ = [("entry_count", C.c_uint64), ("lookup_count", C.c_uint64), ("hit_count", C.c_uint64),
                 ("miss_count", C.c_uint64)]

@@ -891,10 +891,12 @@ int rl_config_load(rl_ctx* c, const rl_config_tree* t) {
   return RL_OK;
 }
 
-int rl_do_limit_requests(rl_ctx* c, const rl_request_batch* in, rl_request_result* out) {
+// rl_do_limit_requests, with the per-request verdict when asked for.
+static int do_limit_requests(rl_ctx* c, const rl_request_batch* in, rl_request_result* out, uint32_t opts,
+                             rl_request_verdict* verdict) {
   if (!c) return fail(c, RL_E_INVALID, "gpu: null ctx");
   if (c->comm) return fail(c, RL_E_INVALID, "gpu: rl_do_limit_requests is not routed (rl_do_limit_routed_async)");
-  if (c->n == 1) return eng_do_limit_requests(c->e[0], in, out);
+  if (c->n == 1) return eng_do_limit_requests(c->e[0], in, out, nullptr, nullptr, opts, verdict);
   // a multi-shard ctx: the config match on shard 0's GPU, the matched batch
   // through the shards as a device batch (shard 0 partitions it, every owner
   // answers its keys), then the expansion to the request layout on shard 0
@@ -911,8 +913,28 @@ int rl_do_limit_requests(rl_ctx* c, const rl_request_batch* in, rl_request_resul
     r.failed = sr || yr;
     return sr ? sr : yr;
   };
-  rc = eng_do_limit_requests(c->e[0], in, out, run, &u);
+  rc = eng_do_limit_requests(c->e[0], in, out, run, &u, opts, verdict);
   return u.failed ? rc : from_engine(c, c->e[0], rc);
+}
+
+int rl_do_limit_requests(rl_ctx* c, const rl_request_batch* in, rl_request_result* out) {
+  return do_limit_requests(c, in, out, 0, nullptr);
+}
+
+int rl_do_limit_requests_verdict(rl_ctx* c, const rl_request_batch* in, rl_request_result* out, uint32_t opts,
+                                 rl_request_verdict* verdict) {
+  if (!c) return fail(c, RL_E_INVALID, "gpu: null ctx");
+  if (!verdict) return fail(c, RL_E_INVALID, "gpu: null rl_request_verdict");
+  return do_limit_requests(c, in, out, opts, verdict);
+}
+
+int rl_debug_verdict(rl_ctx* c, uint32_t n_requests, uint32_t n_descriptors, const uint32_t* req_idx,
+                     const uint8_t* match, const uint8_t* code, const uint32_t* limit_remaining,
+                     const uint32_t* reset_s, const uint32_t* requests_per_unit, uint32_t opts,
+                     rl_request_verdict* verdict) {
+  if (!c) return fail(c, RL_E_INVALID, "gpu: null ctx");
+  return from_engine(c, c->e[0], eng_debug_verdict(c->e[0], n_requests, n_descriptors, req_idx, match, code,
+                                                    limit_remaining, reset_s, requests_per_unit, opts, verdict));
 }
 
 // Diagnostics, profiling and the per-rank routing halves act on shard 0.

@@ -213,8 +213,14 @@ int eng_config_load(Engine* c, const rl_config_tree* tree);
 // ctx's shards): the matched batch and the result arrays in device memory of
 // c's GPU, inputs ready on `st`; returns once the results are complete.
 using RequestsDoLimit = int (*)(void* user, const rl_batch* dev_in, rl_result* dev_out, hipStream_t st);
+// verdict (optional): the per-request verdict after the expansion
+// (rl_do_limit_requests_verdict); out may then be null.
 int eng_do_limit_requests(Engine* c, const rl_request_batch* in, rl_request_result* out, RequestsDoLimit run = nullptr,
-                          void* user = nullptr);
+                          void* user = nullptr, uint32_t opts = 0, rl_request_verdict* verdict = nullptr);
+int eng_debug_verdict(Engine* c, uint32_t n_requests, uint32_t n_descriptors, const uint32_t* req_idx,
+                      const uint8_t* match, const uint8_t* code, const uint32_t* limit_remaining,
+                      const uint32_t* reset_s, const uint32_t* requests_per_unit, uint32_t opts,
+                      rl_request_verdict* verdict);
 int eng_local_cache_info_get(Engine* c, int64_t now, rl_local_cache_info* info);
 int eng_snapshot_size(Engine* c, uint64_t* bytes);
 int eng_snapshot_save(Engine* c, void* host, uint64_t bytes);

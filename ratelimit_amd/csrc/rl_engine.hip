@@ -1514,9 +1514,31 @@ int eng_config_load(Engine* c, const rl_config_tree* t) {
   return RL_OK;
 }
 
+namespace {
+// A finished verdict block (device, verdict_layout(nq)) -> the caller's arrays.
+hipError_t verdict_d2h(const uint8_t* block, uint32_t nq, rl_request_verdict* v, hipStream_t st) {
+  const VerdictLayout L = verdict_layout(nq);
+  hipError_t e = hipSuccess;
+  auto get = [&](void* dst, size_t off, size_t bytes) {
+    if (e == hipSuccess && dst && bytes) e = hipMemcpyAsync(dst, block + off, bytes, hipMemcpyDeviceToHost, st);
+  };
+  get(v->overall_code, L.o_code, nq);
+  get(v->flags, L.o_flags, nq);
+  get(v->min_descriptor, L.o_min, nq * 4ull);
+  get(v->header_limit, L.o_limit, nq * 4ull);
+  get(v->header_remaining, L.o_rem, nq * 4ull);
+  get(v->header_reset_s, L.o_reset, nq * 4ull);
+  get(v->global_shadow, L.shadow, 8);
+  return e;
+}
+}  // namespace
+
 int eng_do_limit_requests(Engine* c, const rl_request_batch* in, rl_request_result* out, RequestsDoLimit run,
-                          void* user) {
-  if (!c || !in || !out) return set_err(c, RL_E_INVALID, "gpu: null argument");
+                          void* user, uint32_t opts, rl_request_verdict* verdict) {
+  if (!c || !in || (!out && !verdict)) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (verdict && in->n_requests && !verdict->overall_code)
+    return set_err(c, RL_E_INVALID, "gpu: rl_request_verdict without overall_code");
+  if (verdict && (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW)) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
   // checkServiceErr(snappedConfig != nil, ...) (ratelimit.go:106)
   if (!c->cfg_loaded) return set_err(c, RL_E_INVALID, "gpu: no rate limit configuration loaded");
   const uint32_t n = in->n_descriptors, nq = in->n_requests, ne = in->n_entries;
@@ -1551,6 +1573,8 @@ int eng_do_limit_requests(Engine* c, const rl_request_batch* in, rl_request_resu
                o_rpu = piece(n * 4ull), o_rule = piece(n * 4ull), o_cnt = piece(16), o_code = piece(n),
                o_rem = piece(n * 4ull), o_reset = piece(n * 4ull), o_match = piece(n), o_orule = piece(n * 4ull),
                o_orpu = piece(n * 4ull), o_ounit = piece(n), o_tmp = piece(scan);
+  const VerdictLayout vl = verdict_layout(nq);
+  const size_t o_verdict = verdict ? piece(vl.bytes) : 0;
   hipStream_t st = c->stream;
   HIPCHK(c, after_batches(c, st));
   if (need > c->mbuf_cap) {
@@ -1649,21 +1673,94 @@ int eng_do_limit_requests(Engine* c, const rl_request_batch* in, rl_request_resu
                (uint32_t*)(B + o_orule), (uint32_t*)(B + o_orpu), B + o_ounit};
   launch_match_expand(r, m, c->d_code, c->d_rem, c->d_reset, ro, st);
   HIPCHK(c, hipGetLastError());
+  if (verdict && nq) {
+    // the verdict reads the expanded answers where they lie
+    const VerdictDev vd = verdict_view(nq, n, opts, r.req, ro.match, ro.code, ro.rem, ro.reset, ro.rpu, B + o_verdict);
+    HIPCHK(c, launch_verdict(vd, B + o_verdict, st));
+  }
   auto d2h = [&](void* dst, size_t off, size_t bytes) {
     return (bytes && dst) ? hipMemcpyAsync(dst, B + off, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
   };
-  HIPCHK(c, d2h(out->code, o_code, n));
-  HIPCHK(c, d2h(out->limit_remaining, o_rem, n * 4ull));
-  HIPCHK(c, d2h(out->reset_s, o_reset, n * 4ull));
-  HIPCHK(c, d2h(out->match, o_match, n));
-  HIPCHK(c, d2h(out->rule_id, o_orule, n * 4ull));
-  HIPCHK(c, d2h(out->requests_per_unit, o_orpu, n * 4ull));
-  HIPCHK(c, d2h(out->unit, o_ounit, n));
-  if (in->n_rules && out->stats)
-    HIPCHK(c, hipMemcpyAsync(out->stats, c->d_stats, (size_t)in->n_rules * RL_NUM_STATS * 8, hipMemcpyDeviceToHost, st));
+  if (out) {
+    HIPCHK(c, d2h(out->code, o_code, n));
+    HIPCHK(c, d2h(out->limit_remaining, o_rem, n * 4ull));
+    HIPCHK(c, d2h(out->reset_s, o_reset, n * 4ull));
+    HIPCHK(c, d2h(out->match, o_match, n));
+    HIPCHK(c, d2h(out->rule_id, o_orule, n * 4ull));
+    HIPCHK(c, d2h(out->requests_per_unit, o_orpu, n * 4ull));
+    HIPCHK(c, d2h(out->unit, o_ounit, n));
+    if (in->n_rules && out->stats)
+      HIPCHK(c, hipMemcpyAsync(out->stats, c->d_stats, (size_t)in->n_rules * RL_NUM_STATS * 8, hipMemcpyDeviceToHost, st));
+  }
   c->batches++;
   c->decisions += nm;
-  return collect(c);
+  const int rc = collect(c);
+  if (rc || !verdict) return rc;
+  // copied only now that the batch is known good: a failed batch leaves *verdict alone
+  if (nq) {
+    HIPCHK(c, verdict_d2h(B + o_verdict, nq, verdict, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+  } else if (verdict->global_shadow) {
+    *verdict->global_shadow = 0;
+  }
+  return RL_OK;
+}
+
+int eng_debug_verdict(Engine* c, uint32_t nq, uint32_t n, const uint32_t* req_idx, const uint8_t* match,
+                      const uint8_t* code, const uint32_t* limit_remaining, const uint32_t* reset_s,
+                      const uint32_t* requests_per_unit, uint32_t opts, rl_request_verdict* verdict) {
+  if (!c || !verdict) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (nq && !verdict->overall_code) return set_err(c, RL_E_INVALID, "gpu: rl_request_verdict without overall_code");
+  if (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
+  if (n > c->cfg.max_batch || nq > c->cfg.max_requests)
+    return set_err(c, RL_E_CAPACITY, "gpu: verdict input exceeds configured max_batch/max_requests");
+  if (n && (!req_idx || !match || !code || !limit_remaining || !reset_s || !requests_per_unit))
+    return set_err(c, RL_E_INVALID, "gpu: null verdict input array");
+  for (uint32_t d = 0; d < n; d++)
+    if (req_idx[d] >= nq || (d && req_idx[d] < req_idx[d - 1]))
+      return set_err(c, RL_E_INVALID, "gpu: req_idx must be non-decreasing and below n_requests");
+  if (!nq) {
+    if (verdict->global_shadow) *verdict->global_shadow = 0;
+    return RL_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const VerdictLayout vl = verdict_layout(nq);
+  size_t need = 0;
+  auto piece = [&need](size_t bytes) {
+    const size_t o = need;
+    need += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
+    return o;
+  };
+  const size_t o_req = piece(n * 4ull), o_match = piece(n), o_code = piece(n), o_rem = piece(n * 4ull),
+               o_reset = piece(n * 4ull), o_rpu = piece(n * 4ull), o_verdict = piece(vl.bytes);
+  uint8_t* B = nullptr;
+  HIPCHK(c, hipMalloc((void**)&B, need));
+  hipStream_t st = c->stream;
+  auto run = [&]() -> hipError_t {
+    hipError_t e = after_batches(c, st);
+    auto h2d = [&](size_t off, const void* src, size_t bytes) {
+      if (e == hipSuccess && bytes) e = hipMemcpyAsync(B + off, src, bytes, hipMemcpyHostToDevice, st);
+    };
+    h2d(o_req, req_idx, n * 4ull);
+    h2d(o_match, match, n);
+    h2d(o_code, code, n);
+    h2d(o_rem, limit_remaining, n * 4ull);
+    h2d(o_reset, reset_s, n * 4ull);
+    h2d(o_rpu, requests_per_unit, n * 4ull);
+    if (e != hipSuccess) return e;
+    const VerdictDev vd = verdict_view(nq, n, opts, (const uint32_t*)(B + o_req), B + o_match, B + o_code,
+                                       (const uint32_t*)(B + o_rem), (const uint32_t*)(B + o_reset),
+                                       (const uint32_t*)(B + o_rpu), B + o_verdict);
+    e = launch_verdict(vd, B + o_verdict, st);
+    if (e != hipSuccess) return e;
+    e = verdict_d2h(B + o_verdict, nq, verdict, st);
+    if (e != hipSuccess) return e;
+    return hipStreamSynchronize(st);
+  };
+  const hipError_t e = run();
+  (void)hipFree(B);
+  HIPCHK(c, e);
+  return RL_OK;
 }
 
 // ---- observability and restart ---------------------------------------------

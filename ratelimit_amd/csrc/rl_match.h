@@ -88,6 +88,51 @@ struct ReqOutDev {
   uint8_t* unit;
 };
 
+// The per-request verdict (rl_request_verdict) on the device: its inputs are
+// the per-descriptor answers, its scratch and outputs one carved block
+//   [inv_min u64 nq | over u32 nq | pad | shadow u64 | min_desc, limit,
+//    remaining, reset u32 nq each | code u8 nq | flags u8 nq]
+// The accumulators (up to and including the shadow count) are zeroed on the
+// stream.
+struct VerdictDev {
+  uint32_t n_req, n_desc, opts;
+  const uint32_t* req;
+  const uint8_t* match;
+  const uint8_t* code;
+  const uint32_t* rem;
+  const uint32_t* reset;
+  const uint32_t* rpu;
+  unsigned long long* inv_min;  // ~min((remaining << 32) | d) over the limited descriptors; 0 = none
+  uint32_t* over;               // max(d + 1) over the OVER_LIMIT descriptors; 0 = none
+  unsigned long long* shadow;   // [1] requests that global shadow mode turned into OK
+  uint32_t* o_min;
+  uint32_t* o_limit;
+  uint32_t* o_rem;
+  uint32_t* o_reset;
+  uint8_t* o_code;
+  uint8_t* o_flags;
+};
+
+struct VerdictLayout {
+  size_t inv_min, over, shadow, o_min, o_limit, o_rem, o_reset, o_code, o_flags, bytes;
+  size_t acc_bytes() const { return shadow + 8; }  // zeroed before the kernels
+};
+inline VerdictLayout verdict_layout(uint32_t nq) {
+  VerdictLayout L;
+  const size_t q = nq;
+  L.inv_min = 0;
+  L.over = 8 * q;
+  L.shadow = (12 * q + 7) & ~(size_t)7;
+  L.o_min = L.shadow + 8;
+  L.o_limit = L.o_min + 4 * q;
+  L.o_rem = L.o_limit + 4 * q;
+  L.o_reset = L.o_rem + 4 * q;
+  L.o_code = L.o_reset + 4 * q;
+  L.o_flags = L.o_code + q;
+  L.bytes = L.o_flags + q;
+  return L;
+}
+
 constexpr uint32_t MATCH_ERR_REQ = 1, MATCH_ERR_CAP = 2;
 
 __host__ __device__ inline uint64_t cfg_hash(int32_t parent, const uint8_t* p, uint32_t len) {
@@ -109,5 +154,13 @@ void launch_match(const CfgDev& cfg, const ReqDev& r, const MatchBuf& m, const P
                   size_t tmp_bytes, hipStream_t st);
 void launch_match_expand(const ReqDev& r, const MatchBuf& m, const uint8_t* code, const uint32_t* rem,
                          const uint32_t* reset, const ReqOutDev& out, hipStream_t st);
+// Enqueue the verdict over per-descriptor answers already on the device
+// (v.req non-decreasing and < v.n_req): zeroes the accumulators at `block`
+// (verdict_layout(v.n_req), whose pointers v holds), then k_verdict and
+// k_verdict_final.
+hipError_t launch_verdict(const VerdictDev& v, uint8_t* block, hipStream_t st);
+VerdictDev verdict_view(uint32_t n_req, uint32_t n_desc, uint32_t opts, const uint32_t* req, const uint8_t* match,
+                        const uint8_t* code, const uint32_t* rem, const uint32_t* reset, const uint32_t* rpu,
+                        uint8_t* block);
 
 }  // namespace rl

@@ -3,7 +3,8 @@
 // constructLimitsToCheck, src/service/ratelimit.go:104-143), compaction of
 // the matched descriptors into the DoLimit batch (the nil / unlimited ones
 // never reach DoLimit, ratelimit.go:140-143 and base_limiter.go:78-81), and
-// the per-descriptor answer of shouldRateLimitWorker (ratelimit.go:176-190).
+// the per-descriptor answer of shouldRateLimitWorker (ratelimit.go:176-190)
+// with, on request, the rest of that function per request.
 //
 // k_match: one lane per descriptor. The config trie is an open-addressing
 // index of (parent node, key bytes) -> node, a few KB that stays in L2; the
@@ -14,7 +15,9 @@
 // k_match_emit writes the DoLimit arrays and the stem
 //   prefix ‖ domain ‖ '_' ‖ Σ(key ‖ '_' ‖ value ‖ '_')   (cache_key.go:62-71)
 // (the descriptor's entry bytes already are the tail). k_match_expand maps the
-// DoLimit results back to every descriptor.
+// DoLimit results back to every descriptor. k_verdict / k_verdict_final reduce
+// them to the answer per request (ratelimit.go:163-209): the overall code, the
+// header descriptor's values and global shadow mode.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -277,7 +280,137 @@ __global__ __launch_bounds__(256) void k_match_expand(ReqDev r, MatchBuf m, cons
   out.unit[d] = (uint8_t)(k >> 8);
 }
 
+// The rest of shouldRateLimitWorker (ratelimit.go:163-209, customHeadersEnabled):
+// OverallCode and the descriptor "closest to its limit" behind the
+// RateLimit-* headers. The reference's loop is order-dependent, but its result
+// has a closed form over a request's descriptors (contiguous in the batch):
+//   any OVER_LIMIT status  -> OVER_LIMIT, minimumDescriptor = the LAST such d
+//                             (:185-190 overwrite it and pin minLimitRemaining to 0);
+//   otherwise              -> OK, minimumDescriptor = the FIRST limited d with
+//                             the smallest LimitRemaining (strict <, :173), none
+//                             below MaxUint32 -> nil (minLimitRemaining starts there, :166).
+// Both are order-free reductions: over[q] = max(d + 1) and
+// min[q] = min(remaining << 32 | d), kept as ~min so that one zeroing
+// initialises both.
+//
+// k_verdict: one lane per descriptor. A segmented inclusive scan over the
+// wave's runs of equal req_idx (cross-lane shuffles; a lane combines with the
+// lane `off` below only inside its own run) leaves each run's reduction in its
+// last lane. A run that is the whole request (the usual case) is stored
+// plainly; a request that continues in a neighbouring wave gets one atomic
+// pair per (wave, request) segment.
+__global__ __launch_bounds__(256) void k_verdict(VerdictDev v) {
+  const uint32_t d = blockIdx.x * 256 + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool in = d < v.n_desc;
+  const uint32_t q = in ? v.req[d] : 0xFFFFFFFFu;  // (no request has this index: n_req <= 2^32 - 1)
+  uint32_t ov = 0;
+  unsigned long long mn = ~0ull;
+  if (in && v.match[d] == RL_MATCH_LIMIT) {  // CurrentLimit != nil (:172); unlimited ones carry none
+    const uint32_t rm = v.rem[d];
+    if (v.code[d] == RL_CODE_OVER_LIMIT) ov = d + 1u;
+    if (rm != 0xFFFFFFFFu) mn = (unsigned long long)rm << 32 | d;
+  }
+  const uint32_t qp = __shfl_up(q, 1);
+  const unsigned long long heads = __ballot(lane == 0 || qp != q);
+  const int hl = 63 - __clzll(heads & (~0ull >> (63u - lane)));  // first lane of this lane's run
+  for (uint32_t off = 1; off < 64; off <<= 1) {
+    const uint32_t to = __shfl_up(ov, off);
+    const unsigned long long tm = __shfl_up(mn, off);
+    if ((int)lane - (int)off >= hl) {
+      ov = max(ov, to);
+      mn = min(mn, tm);
+    }
+  }
+  const uint32_t qn = __shfl_down(q, 1);
+  if (!in || q >= v.n_req || !(lane == 63 || qn != q)) return;
+  // the run's last lane: does the request go on in another wave?
+  bool open = false;
+  if (hl == 0) {
+    const uint32_t d0 = d - lane;
+    open = d0 > 0 && v.req[d0 - 1] == q;
+  }
+  if (!open && lane == 63) open = d + 1u < v.n_desc && v.req[d + 1] == q;
+  if (!open) {
+    v.over[q] = ov;
+    v.inv_min[q] = ~mn;
+  } else {
+    if (ov) atomicMax(v.over + q, ov);
+    if (mn != ~0ull) atomicMax(v.inv_min + q, ~mn);
+  }
+}
+
+// One lane per request: the chosen descriptor's header values
+// (rateLimitLimitHeader / RemainingHeader / ResetHeader, ratelimit.go:213-237),
+// global shadow mode (:203-207) and its counter: one ballot and one atomic per wave.
+__global__ __launch_bounds__(256) void k_verdict_final(VerdictDev v) {
+  const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+  bool shadowed = false;
+  if (q < v.n_req) {
+    const uint32_t ov = v.over[q];
+    const unsigned long long im = v.inv_min[q];
+    uint32_t d = RL_NO_DESCRIPTOR, fl = 0;
+    uint8_t code = RL_CODE_OK;
+    if (ov) {
+      d = ov - 1u;
+      code = RL_CODE_OVER_LIMIT;
+      fl = RL_VERDICT_OVER_LIMIT;
+      if (v.opts & RL_VERDICT_OPT_GLOBAL_SHADOW) {
+        code = RL_CODE_OK;
+        fl |= RL_VERDICT_GLOBAL_SHADOW;
+        shadowed = true;
+      }
+    } else if (im) {
+      d = (uint32_t)~im;
+    }
+    const bool has = d < v.n_desc;
+    v.o_min[q] = has ? d : RL_NO_DESCRIPTOR;
+    v.o_limit[q] = has ? v.rpu[d] : 0u;
+    v.o_rem[q] = has ? v.rem[d] : 0u;
+    v.o_reset[q] = has ? v.reset[d] : 0u;
+    v.o_code[q] = code;
+    v.o_flags[q] = (uint8_t)fl;
+  }
+  const unsigned long long b = __ballot(shadowed);
+  if ((threadIdx.x & 63u) == 0 && b) atomicAdd(v.shadow, (unsigned long long)__popcll(b));
+}
+
 }  // namespace
+
+VerdictDev verdict_view(uint32_t n_req, uint32_t n_desc, uint32_t opts, const uint32_t* req, const uint8_t* match,
+                        const uint8_t* code, const uint32_t* rem, const uint32_t* reset, const uint32_t* rpu,
+                        uint8_t* block) {
+  const VerdictLayout L = verdict_layout(n_req);
+  VerdictDev v;
+  v.n_req = n_req;
+  v.n_desc = n_desc;
+  v.opts = opts;
+  v.req = req;
+  v.match = match;
+  v.code = code;
+  v.rem = rem;
+  v.reset = reset;
+  v.rpu = rpu;
+  v.inv_min = (unsigned long long*)(block + L.inv_min);
+  v.over = (uint32_t*)(block + L.over);
+  v.shadow = (unsigned long long*)(block + L.shadow);
+  v.o_min = (uint32_t*)(block + L.o_min);
+  v.o_limit = (uint32_t*)(block + L.o_limit);
+  v.o_rem = (uint32_t*)(block + L.o_rem);
+  v.o_reset = (uint32_t*)(block + L.o_reset);
+  v.o_code = block + L.o_code;
+  v.o_flags = block + L.o_flags;
+  return v;
+}
+
+hipError_t launch_verdict(const VerdictDev& v, uint8_t* block, hipStream_t st) {
+  if (!v.n_req) return hipSuccess;
+  const hipError_t e = hipMemsetAsync(block, 0, verdict_layout(v.n_req).acc_bytes(), st);
+  if (e != hipSuccess) return e;
+  if (v.n_desc) k_verdict<<<(v.n_desc + 255) / 256, 256, 0, st>>>(v);
+  k_verdict_final<<<(v.n_req + 255) / 256, 256, 0, st>>>(v);
+  return hipGetLastError();
+}
 
 size_t match_scan_bytes(uint32_t n) {
   size_t bytes = 0;

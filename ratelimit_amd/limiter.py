@@ -30,7 +30,8 @@ from .types import OK, DescriptorStatus, Limit  # noqa: F401  (re-exported data 
 STAGES = ("prepare", "sort", "segment", "table", "finish")
 PROFILE_FIELDS = STAGES + ("table_kernel",)  # + k_table's own run time (device clock)
 
-__all__ = ["GpuRateLimitCache", "GpuRateLimitService", "KeyState", "RedisError", "TimeSource", "migrate"]
+__all__ = ["GpuRateLimitCache", "GpuRateLimitService", "KeyState", "RedisError", "RequestVerdict", "TimeSource",
+           "migrate"]
 
 
 class KeyState(NamedTuple):
@@ -255,6 +256,61 @@ class Backend:
         self._check(self.L.rl_do_limit_requests(self.ctx, C.byref(b), C.byref(r)))
         res = {k: v[:n] for k, v in out.items() if k != "stats"}
         res["stats"] = out["stats"][:n_rules * abi.RL_NUM_STATS]
+        return res
+
+    def do_limit_requests_verdict(self, arrays: dict, n_rules: int, global_shadow: bool = False,
+                                  per_descriptor: bool = True, stats: bool = True) -> dict:
+        """rl_do_limit_requests_verdict on pack_requests() arrays -> the per-request
+        verdict arrays (abi.REQUEST_VERDICT_DTYPES) and ``global_shadow`` (this
+        call's count), with do_limit_requests' per-descriptor arrays when
+        ``per_descriptor`` and the per-rule ``stats`` deltas when ``stats``; with
+        neither, ``out`` is NULL and only per-request bytes come back."""
+        n, nq = len(arrays["req_idx"]), len(arrays["hits"])
+        b = abi.RlRequestBatch()
+        b.n_requests, b.n_descriptors, b.n_entries, b.n_rules = nq, n, len(arrays["key_len"]), n_rules
+        for k in abi.REQUEST_ARRAYS:
+            setattr(b, k, abi.ptr(arrays[k]))
+        out = {}
+        if per_descriptor:
+            out = {k: np.zeros(max(n, 1), dt) for k, dt in abi.REQUEST_RESULT_DTYPES.items()}
+        if stats:
+            out["stats"] = np.zeros(max(n_rules, 1) * abi.RL_NUM_STATS, np.uint64)
+        r = abi.RlRequestResult()
+        for k in out:
+            setattr(r, k, abi.ptr(out[k]))
+        ver = {k: np.zeros(max(nq, 1), dt) for k, dt in abi.REQUEST_VERDICT_DTYPES.items()}
+        gs = np.zeros(1, np.uint64)
+        v = abi.RlRequestVerdict()
+        for k in ver:
+            setattr(v, k, abi.ptr(ver[k]))
+        v.global_shadow = abi.ptr(gs)
+        opts = abi.RL_VERDICT_OPT_GLOBAL_SHADOW if global_shadow else 0
+        self._check(self.L.rl_do_limit_requests_verdict(self.ctx, C.byref(b), C.byref(r) if out else None, opts,
+                                                         C.byref(v)))
+        res = {k: a[:n] for k, a in out.items() if k != "stats"}
+        if stats:
+            res["stats"] = out["stats"][:n_rules * abi.RL_NUM_STATS]
+        res.update({k: a[:nq] for k, a in ver.items()})
+        res["global_shadow"] = int(gs[0])
+        return res
+
+    def debug_verdict(self, n_requests, req_idx, match, code, limit_remaining, reset_s, requests_per_unit,
+                      global_shadow: bool = False) -> dict:
+        """rl_debug_verdict: the device verdict alone on explicit per-descriptor answers."""
+        a = [np.ascontiguousarray(x, dt) for x, dt in
+             ((req_idx, np.uint32), (match, np.uint8), (code, np.uint8), (limit_remaining, np.uint32),
+              (reset_s, np.uint32), (requests_per_unit, np.uint32))]
+        ver = {k: np.zeros(max(n_requests, 1), dt) for k, dt in abi.REQUEST_VERDICT_DTYPES.items()}
+        gs = np.zeros(1, np.uint64)
+        v = abi.RlRequestVerdict()
+        for k in ver:
+            setattr(v, k, abi.ptr(ver[k]))
+        v.global_shadow = abi.ptr(gs)
+        opts = abi.RL_VERDICT_OPT_GLOBAL_SHADOW if global_shadow else 0
+        self._check(self.L.rl_debug_verdict(self.ctx, n_requests, len(a[0]), *[abi.ptr(x) for x in a], opts,
+                                             C.byref(v)))
+        res = {k: x[:n_requests] for k, x in ver.items()}
+        res["global_shadow"] = int(gs[0])
         return res
 
     def profile(self, enable: bool, every: int = 1):
@@ -611,11 +667,21 @@ class GpuRateLimitCache:
         return None
 
 
+class RequestVerdict(NamedTuple):
+    """One request's answer from should_rate_limit_verdicts."""
+    code: int                       # RateLimitResponse.OverallCode
+    flags: int                      # abi.RL_VERDICT_*
+    headers: Optional[tuple]        # (limit, remaining, reset seconds) of the minimumDescriptor, or None
+    statuses: Optional[list]        # [DescriptorStatus], or None when not asked for
+
+
 class GpuRateLimitService:
     """The service step around DoLimit with the config lookup on the GPU:
     constructLimitsToCheck + DoLimit + shouldRateLimitWorker's statuses
-    (src/service/ratelimit.go:104-208; no custom headers) for many requests at
-    once through ``rl_do_limit_requests``. Config is YAML text as
+    (src/service/ratelimit.go:104-208) for many requests at once through
+    ``rl_do_limit_requests``; should_rate_limit_verdicts also takes the overall
+    code, the RateLimit-* header values and global shadow mode from the device
+    (``rl_do_limit_requests_verdict``, ratelimit.go:163-209). Config is YAML text as
     ``NewRateLimitConfigImpl`` takes it (src/config/config_impl.go:318-330)."""
 
     def __init__(self, config_files, near_limit_ratio: float = 0.8, local_cache: bool = False,
@@ -628,9 +694,56 @@ class GpuRateLimitService:
         self.backend = Backend(near_limit_ratio, local_cache, per_second, **backend_kw)
         self.backend.load_config(self.tree)
         self.stats = {}  # stats key -> [6 counters] (the gostats store)
+        self.global_shadow_count = 0  # stats.GlobalShadowMode (should_rate_limit_verdicts)
 
     def close(self):
         self.backend.close()
+
+    def _add_stats(self, deltas):
+        st = deltas.reshape(-1, abi.RL_NUM_STATS)
+        for i in np.nonzero(st.any(axis=1))[0]:
+            row = self.stats.setdefault(self.interner.keys[i], [0] * abi.RL_NUM_STATS)
+            for j in range(abi.RL_NUM_STATS):
+                row[j] += int(st[i, j])
+
+    def should_rate_limit_verdicts(self, requests, nows, per_descriptor: bool = True):
+        """-> ([RequestVerdict] per request in arrival order, this call's
+        global-shadow count). The overall code, the flags and the header triple
+        (limit, remaining, reset seconds; None without a minimumDescriptor) come
+        from the device; ``statuses`` is the [DescriptorStatus] list when
+        ``per_descriptor``, else None: then only per-request bytes and the
+        per-rule stats deltas cross PCIe."""
+        from .config import pack_requests
+        for r in requests:  # checkServiceErr (ratelimit.go:151-152)
+            if r.domain == "":
+                raise ValueError("rate limit domain must not be empty")
+            if not r.descriptors:
+                raise ValueError("rate limit descriptor list must not be empty")
+        a = pack_requests(requests, nows, self.interner)
+        n_rules = max(len(self.interner.keys), 1)
+        res = self.backend.do_limit_requests_verdict(a, n_rules, self.global_shadow_mode, per_descriptor)
+        self._add_stats(res["stats"])
+        self.global_shadow_count += res["global_shadow"]
+        out = []
+        d = 0
+        for q, r in enumerate(requests):
+            sts = None
+            if per_descriptor:
+                sts = []
+                for _ in r.descriptors:
+                    if int(res["match"][d]) == abi.RL_MATCH_LIMIT:
+                        sts.append(DescriptorStatus(int(res["code"][d]),
+                                                    Limit(int(res["requests_per_unit"][d]), int(res["unit"][d])),
+                                                    int(res["limit_remaining"][d]), int(res["reset_s"][d])))
+                    else:  # nil limit {OK, nil, 0}; unlimited {OK, nil, MaxUint32}
+                        sts.append(DescriptorStatus(OK, None, int(res["limit_remaining"][d]), None))
+                    d += 1
+            headers = None
+            if int(res["min_descriptor"][q]) != abi.RL_NO_DESCRIPTOR:
+                headers = (int(res["header_limit"][q]), int(res["header_remaining"][q]),
+                           int(res["header_reset_s"][q]))
+            out.append(RequestVerdict(int(res["overall_code"][q]), int(res["flags"][q]), headers, sts))
+        return out, res["global_shadow"]
 
     def should_rate_limit_batch(self, requests, nows):
         """-> [(overall code, [DescriptorStatus])] per request, arrival order."""

@@ -8,7 +8,12 @@ mid-call count readback. The same batches through the packed DoLimit path
 (rl_do_limit, also host buffers) are timed beside it, and both results are
 checked equal (the request path must give DoLimit's answers).
 
-    python scripts/bench_requests.py [--config c1|c2] [--steps K]
+--verdict full adds the per-request verdict (rl_do_limit_requests_verdict:
+overall code, header values, global shadow mode); --verdict only also drops
+the per-descriptor outputs (out == NULL), so that only per-request bytes come
+back. off (the default) is rl_do_limit_requests as before.
+
+    python scripts/bench_requests.py [--config c1|c2] [--steps K] [--verdict off|full|only]
 """
 import argparse
 import ctypes as C
@@ -42,6 +47,7 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--requests", type=int, default=500_000)
     ap.add_argument("--tenants", type=int, default=10_000_000)
+    ap.add_argument("--verdict", default="off", choices=["off", "full", "only"])
     args = ap.parse_args()
     nq, T = args.requests, args.tenants
     rng = np.random.default_rng(0xC1 if args.config == "c1" else 0xC2)
@@ -65,6 +71,12 @@ def main():
     pr = {k: pinned(np.zeros(n, dt)) for k, dt in abi.RESULT_DTYPES.items() if k != "stats"}
     pr["stats"] = pinned(np.zeros(2 * abi.RL_NUM_STATS, np.uint64))
 
+    vr = {k: pinned(np.zeros(nq, dt)) for k, dt in abi.REQUEST_VERDICT_DTYPES.items()}
+    vr["global_shadow"] = pinned(np.zeros(1, np.uint64))
+    d2h = {"off": 0, "full": 18 * nq + 8, "only": 18 * nq + 8}[args.verdict]  # bytes per call, stats apart
+    if args.verdict != "only":
+        d2h += sum(v.nbytes for k, v in rr.items() if k != "stats")
+
     def req_call(raw):
         b = abi.RlRequestBatch()
         b.n_requests, b.n_descriptors, b.n_entries, b.n_rules = nq, n, 2 * n, 2
@@ -73,7 +85,14 @@ def main():
         r = abi.RlRequestResult()
         for k in rr:
             setattr(r, k, abi.ptr(rr[k]))
-        rc = lib().rl_do_limit_requests(be_req.ctx, C.byref(b), C.byref(r))
+        if args.verdict == "off":
+            rc = lib().rl_do_limit_requests(be_req.ctx, C.byref(b), C.byref(r))
+        else:
+            v = abi.RlRequestVerdict()
+            for k in vr:
+                setattr(v, k, abi.ptr(vr[k]))
+            rp = C.byref(r) if args.verdict == "full" else None
+            rc = lib().rl_do_limit_requests_verdict(be_req.ctx, C.byref(b), rp, 0, C.byref(v))
         assert rc == 0, lib().rl_last_error(be_req.ctx)
 
     def pk_call(pk):
@@ -90,10 +109,15 @@ def main():
         pk["now"][:] = now
         req_call(raw)
         pk_call(pk)
-        for k in ("code", "limit_remaining", "reset_s"):
-            assert np.array_equal(rr[k], pr[k]), k
-        assert np.array_equal(rr["stats"], pr["stats"])
-        assert (rr["match"] == abi.RL_MATCH_LIMIT).all()
+        if args.verdict != "only":
+            for k in ("code", "limit_remaining", "reset_s"):
+                assert np.array_equal(rr[k], pr[k]), k
+            assert np.array_equal(rr["stats"], pr["stats"])
+            assert (rr["match"] == abi.RL_MATCH_LIMIT).all()
+        if args.verdict != "off":  # the overall code against the packed path's per-descriptor codes
+            want = np.ones(nq, np.uint8)
+            np.maximum.at(want, raw["req_idx"], pr["code"])
+            assert np.array_equal(vr["overall_code"], want), "overall_code"
     res = {}
     for name, fn, idx in (("requests", req_call, 0), ("packed", pk_call, 1)):
         t0 = time.perf_counter()
@@ -102,7 +126,9 @@ def main():
             bt["now"][:] = W.NOW0 + 8 + s
             fn(bt)
         res[name] = time.perf_counter() - t0
-    out = {"path": "rl_do_limit_requests (host buffers, PCIe-inclusive)", "config": args.config.upper(),
+    path = "rl_do_limit_requests" if args.verdict == "off" else "rl_do_limit_requests_verdict"
+    out = {"path": path + " (host buffers, PCIe-inclusive)", "config": args.config.upper(),
+           "verdict": args.verdict, "d2h_bytes_per_descriptor": d2h / n,
            "descriptors_per_batch": n, "steps": args.steps,
            "requests_decisions_per_s": n * args.steps / res["requests"],
            "requests_ms_per_batch": 1e3 * res["requests"] / args.steps,
