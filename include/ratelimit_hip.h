@@ -643,6 +643,106 @@ typedef struct rl_request_verdict {   /* host memory, one entry per request */
  * nothing to *verdict's arrays. */
 int rl_do_limit_requests_verdict(rl_ctx* ctx, const rl_request_batch* in, rl_request_result* out,
                                  uint32_t opts, rl_request_verdict* verdict);
+/* ---- One-buffer raw requests: the request path, pipelined ---------------
+ * The batch of rl_request_batch laid out for the link, like rl_batch_prefixed:
+ * one pinned buffer that crosses PCIe in one copy and is unpacked on the GPU.
+ * req_idx, entry_first, desc_off and domain_off do not cross: a request
+ * carries its descriptor count and domain length, a descriptor its entry
+ * count, and a descriptor's bytes are the sum of key_len + value_len + 2 over
+ * its entries. key_len, value_len, the domain bytes and the entry bytes are
+ * used where they land on the device. Requests form tiles of RL_REQUESTS_TILE;
+ * the index holds each tile's starting offsets, so every tile is unpacked
+ * independently. Overrides (RateLimitDescriptor.Limit) are a sparse list.
+ * Answers, errors and statuses are those of rl_do_limit_requests_verdict on
+ * the equivalent rl_request_batch. Malformed input:
+ *  - a section outside buf or not 4-byte aligned, an index whose entry 0 is
+ *    not zero or whose last entry is not {n_descriptors, n_entries, domain
+ *    bytes, entry bytes}: RL_E_INVALID at the call;
+ *  - sizes over max_batch / max_requests / max_rules, entry bytes over
+ *    max_stem_bytes: RL_E_CAPACITY at the call;
+ *  - a tile whose index entry does not match the sums of its requests'
+ *    descriptor counts and domain lengths, its descriptors' entry counts or
+ *    its entries' lengths; an override whose descriptor is >= n_descriptors or
+ *    not above the one before it, or whose reserved bytes are not zero: the
+ *    batch fails with RL_E_INVALID at rl_synchronize, the table untouched. */
+#define RL_REQUESTS_TILE 256u
+typedef struct rl_request_override {   /* sparse: only descriptors carrying RateLimitDescriptor.Limit */
+  uint32_t descriptor;                 /* batch index, strictly increasing over the list */
+  uint32_t requests_per_unit;
+  uint32_t rule_id;                    /* override_rule of rl_request_batch */
+  uint8_t unit;                        /* pb_type.RateLimitUnit */
+  uint8_t reserved[3];                 /* zero */
+} rl_request_override;
+
+typedef struct rl_request_batch_packed {
+  uint32_t n_requests;
+  uint32_t n_descriptors;
+  uint32_t n_entries;
+  uint32_t n_rules;         /* every rule id (config and override) < n_rules */
+  uint32_t n_overrides;
+  uint32_t reserved;        /* zero */
+  const uint8_t* buf;       /* pinned host memory (rl_alloc_host): copied once, asynchronously */
+  uint64_t buf_bytes;
+  /* sections of buf, as byte offsets (each a multiple of 4, in any order) */
+  uint64_t req;             /* uint32[n_requests]: descriptors of the request (bits 0-15) | bytes of
+                               its domain (bits 16-31) << 16. A request's descriptors follow those
+                               of the request before it */
+  uint64_t now;             /* uint32[n_requests] UnixNow() (< 2^32 - 172800, as rl_batch.now) */
+  uint64_t hits;            /* uint32[n_requests] HitsAddend */
+  uint64_t desc;            /* uint16[n_descriptors]: entries of the descriptor; a descriptor's
+                               entries follow those of the descriptor before it */
+  uint64_t key_len;         /* uint16[n_entries] */
+  uint64_t value_len;       /* uint16[n_entries] */
+  uint64_t domain_bytes;    /* the requests' domains, concatenated in request order */
+  uint64_t entry_bytes;     /* Σ(key ‖ '_' ‖ value ‖ '_') in entry order: rl_request_batch.desc_bytes */
+  uint64_t overrides;       /* rl_request_override[n_overrides] */
+  uint64_t index;           /* uint32[4 x (tiles + 1)], tiles = ceil(n_requests / RL_REQUESTS_TILE):
+                               entry t = {first descriptor, first entry, first domain byte, first
+                               entry byte} of requests [t x TILE, (t+1) x TILE); entry 0 is zero,
+                               entry `tiles` the totals {n_descriptors, n_entries, domain bytes,
+                               entry bytes (<= max_stem_bytes)} */
+} rl_request_batch_packed;
+
+/* rl_request_batch -> rl_request_batch_packed: writes the sections and the
+ * tile index into buf and fills *out (out->buf = buf). Host code; no GPU
+ * needed. A batcher runs rl_packer_pack and then this; `in` is only read.
+ * buf == NULL or buf_cap too small: RL_E_CAPACITY with out->buf_bytes = the
+ * bytes needed and nothing else written. RL_E_INVALID (nothing written):
+ * offsets that do not start at 0, are not monotone or do not end at
+ * n_entries; req_idx decreasing or >= n_requests; a request with more than
+ * 65535 descriptors, a descriptor with more than 65535 entries, a domain
+ * longer than 65535 bytes; a descriptor whose desc_off span is not the sum of
+ * its entries' lengths plus separators; a now outside [0, 2^32). Only bit 0
+ * of override_flags travels. */
+int rl_request_batch_pack(const rl_request_batch* in, uint8_t* buf, uint64_t buf_cap,
+                          rl_request_batch_packed* out);
+
+/* rl_do_limit_requests_verdict on a packed batch, without waiting: the call
+ * returns once the batch's copy, unpack and config match are enqueued. The
+ * DoLimit pipeline needs the matched count on the host, so a batch's second
+ * half (pipeline, expansion, verdict, outputs) is enqueued by a later call of
+ * this entry point, by rl_batch_progress or by rl_synchronize, in submission
+ * order, once its count has arrived; at most RL_REQUESTS_INFLIGHT batches wait
+ * for theirs (a further call waits for the oldest one's count only). Every
+ * other entry point first completes the pending batches, so calls interleaved
+ * with other paths keep submission order. out and verdict may each be NULL
+ * (not both), as may any array inside them: those are not copied back. *out
+ * and *verdict are read after rl_synchronize, or once rl_batch_progress counts
+ * the batch complete; buf stays untouched until then, and so must *in's index
+ * until the call returns. A batch that fails in the match stage (malformed
+ * content, matched stems over max_stem_bytes) skips its second half and leaves
+ * the table untouched; the next rl_synchronize reports the first such failure
+ * since the last one, that batch's outputs are unspecified and later batches
+ * run normally. Pipeline-stage failures are those of rl_do_limit_host_async.
+ * Single-shard ctxs only: a multi-shard ctx or one that joined a communicator
+ * gets RL_E_INVALID (use rl_do_limit_requests_verdict there). */
+#ifndef RL_REQUESTS_INFLIGHT
+#define RL_REQUESTS_INFLIGHT 4u
+#endif
+int rl_do_limit_requests_packed_async(rl_ctx* ctx, const rl_request_batch_packed* in,
+                                      rl_request_result* out, uint32_t opts,
+                                      rl_request_verdict* verdict);
+
 /* Diagnostics (parity tests, like rl_debug_decide): the device verdict alone on
  * explicit per-descriptor answers in host arrays. req_idx must be non-decreasing
  * and < n_requests (RL_E_INVALID); n_descriptors <= max_batch and n_requests <=

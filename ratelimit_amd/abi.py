@@ -128,6 +128,26 @@ class RlRequestVerdict(C.Structure):
                 ("header_remaining", P), ("header_reset_s", P), ("global_shadow", P)]
 
 
+RL_REQUESTS_TILE = 256  # include/ratelimit_hip.h
+RL_REQUESTS_INFLIGHT = 4  # include/ratelimit_hip.h (packed request batches waiting for their second half)
+
+
+class RlRequestOverride(C.Structure):
+    """rl_request_override: one entry of a packed request batch's sparse override list."""
+    _fields_ = [("descriptor", C.c_uint32), ("requests_per_unit", C.c_uint32), ("rule_id", C.c_uint32),
+                ("unit", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class RlRequestBatchPacked(C.Structure):
+    """rl_request_batch_packed: rl_request_batch in one pinned buffer (sections as byte offsets)."""
+    _fields_ = [("n_requests", C.c_uint32), ("n_descriptors", C.c_uint32), ("n_entries", C.c_uint32),
+                ("n_rules", C.c_uint32), ("n_overrides", C.c_uint32), ("reserved", C.c_uint32), ("buf", P),
+                ("buf_bytes", C.c_uint64), ("req", C.c_uint64), ("now", C.c_uint64), ("hits", C.c_uint64),
+                ("desc", C.c_uint64), ("key_len", C.c_uint64), ("value_len", C.c_uint64),
+                ("domain_bytes", C.c_uint64), ("entry_bytes", C.c_uint64), ("overrides", C.c_uint64),
+                ("index", C.c_uint64)]
+
+
 # the per-request arrays of rl_request_verdict (global_shadow apart: one uint64)
 REQUEST_VERDICT_DTYPES = {"overall_code": np.uint8, "flags": np.uint8, "min_descriptor": np.uint32,
                           "header_limit": np.uint32, "header_remaining": np.uint32, "header_reset_s": np.uint32}

@@ -46,6 +46,31 @@ struct HostSlot {
   hipEvent_t out_done = nullptr;  // its outputs are back on the host (the slot is free)
 };
 
+// One packed request batch in flight (eng_do_limit_requests_packed_async). Its
+// first half (the buffer's copy into h.cbuf, k_unpack_requests, the config
+// match and the matched count's way to h_cnt) is enqueued at the call; its
+// second half (the DoLimit pipeline on the matched batch staged in h, the
+// expansion, the verdict, the outputs) once count_done has fired, since
+// enqueue needs the matched count on the host.
+struct RequestSlot {
+  HostSlot h;                    // the matched batch, the clocks and DoLimit's answers; cbuf: the batch's buffer
+  uint8_t* mbuf = nullptr;       // the carved device buffer (the arrays k_unpack_requests and the match write)
+  size_t mbuf_cap = 0;
+  uint32_t* h_cnt = nullptr;     // pinned [4]: matched count, stem bytes, error bits
+  hipEvent_t count_done = nullptr;
+  hipStream_t st = nullptr;      // the pipeline stream of the slot's latest work (its next batch follows on it)
+  // the batch whose second half is pending
+  uint32_t n = 0, nq = 0, n_rules = 0, opts = 0;
+  uint64_t seq = 0;              // its place in the progress ring
+  ReqDev r{};
+  MatchBuf m{};
+  ReqOutDev ro{};
+  uint8_t* vblock = nullptr;     // verdict_layout(nq), or null
+  rl_request_result out{};
+  rl_request_verdict verdict{};
+  bool has_out = false, has_verdict = false;
+};
+
 struct Engine {
   rl_config cfg;
   hipStream_t stream = nullptr;   // serial work (== pipe[0])
@@ -139,6 +164,15 @@ struct Engine {
   uint8_t* mbuf = nullptr;
   size_t mbuf_cap = 0;
   uint32_t* h_match = nullptr;  // pinned [4]: matched count, stem bytes, error bits
+  // packed request batches in flight: a ring of RL_REQUESTS_INFLIGHT slots
+  // (allocated on first use); the rq_n batches from rq_head on wait for their
+  // second half, in submission order. rq_fail: the first match-stage failure
+  // since the last eng_synchronize, which reports it.
+  RequestSlot* rq = nullptr;
+  hipStream_t rq_copy = nullptr;  // the batches' input copies, one after the other
+  uint32_t rq_head = 0, rq_n = 0;
+  int rq_fail = 0;
+  std::string rq_fail_msg;
   // host-fed async batches: NBUF staging slots and two copy streams, so that
   // batch t+1's inputs cross PCIe and batch t-1's outputs come back while
   // batch t's kernels run (allocated on first use)
@@ -217,6 +251,18 @@ using RequestsDoLimit = int (*)(void* user, const rl_batch* dev_in, rl_result* d
 // (rl_do_limit_requests_verdict); out may then be null.
 int eng_do_limit_requests(Engine* c, const rl_request_batch* in, rl_request_result* out, RequestsDoLimit run = nullptr,
                           void* user = nullptr, uint32_t opts = 0, rl_request_verdict* verdict = nullptr);
+// rl_do_limit_requests_packed_async on this engine, and its host-side checks
+// (sizes, sections, the index's ends; no GPU work); *tiles = its request tiles.
+int eng_requests_packed_check(Engine* c, const rl_request_batch_packed* in, const rl_request_result* out, uint32_t opts,
+                              const rl_request_verdict* verdict, uint32_t* tiles);
+int eng_do_limit_requests_packed_async(Engine* c, const rl_request_batch_packed* in, rl_request_result* out,
+                                       uint32_t opts, rl_request_verdict* verdict);
+// Enqueue the second halves of the oldest pending packed request batches, in
+// submission order: the first `must` of them after waiting for their counts,
+// then every further one whose count has already arrived (hipEventQuery).
+// Every engine entry point but the packed one and eng_batch_progress passes
+// rq_n: the calls of all paths then take effect in submission order.
+int eng_requests_advance(Engine* c, uint32_t must);
 int eng_debug_verdict(Engine* c, uint32_t n_requests, uint32_t n_descriptors, const uint32_t* req_idx,
                       const uint8_t* match, const uint8_t* code, const uint32_t* limit_remaining,
                       const uint32_t* reset_s, const uint32_t* requests_per_unit, uint32_t opts,

@@ -81,6 +81,16 @@ int set_err(Engine* c, int code, const std::string& msg) {
       return set_err((c), RL_E_HIP, std::string("gpu: ") + #expr + ": " + hipGetErrorString(_e)); \
   } while (0)
 
+// Every entry point but the packed request one and eng_batch_progress starts
+// by completing the pending packed request batches (eng_requests_advance).
+#define RQ_SETTLE(c)                                               \
+  do {                                                             \
+    if ((c)->rq_n) {                                               \
+      const int _rc = rl::eng_requests_advance((c), (c)->rq_n);    \
+      if (_rc) return _rc;                                         \
+    }                                                              \
+  } while (0)
+
 template <typename T>
 hipError_t dalloc(T** p, size_t count) {
   return hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
@@ -542,6 +552,9 @@ void free_host_slots(Engine* c) {
 }
 
 void copy_time_fold(Engine* c, bool all);
+namespace {
+void free_request_slots(Engine* c);
+}
 
 void eng_destroy(Engine* c) {
   if (!c) return;
@@ -564,6 +577,10 @@ void eng_destroy(Engine* c) {
   if (c->hs_ready) {
     (void)hipDeviceSynchronize();
     free_host_slots(c);
+  }
+  if (c->rq) {  // (pending second halves are dropped with the ctx)
+    (void)hipDeviceSynchronize();
+    free_request_slots(c);
   }
   for (uint32_t k = 0; k < NBUF; k++)
     if (c->pipe[k]) (void)hipStreamSynchronize(c->pipe[k]);
@@ -610,6 +627,7 @@ void eng_destroy(Engine* c) {
 
 int eng_do_limit_async(Engine* c, const rl_batch* in, rl_result* out, void* stream) {
   if (!c || !in || !out) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   // device pointers: the total stem size is only known on the device; the
   // kernels bound-check offsets against max_stem_bytes (stem_cap)
   int rc = check_sizes(c, in, 0);
@@ -670,6 +688,7 @@ int eng_route_pack(Engine* c, const rl_batch* in, uint32_t n_shards, uint32_t sr
                    unsigned long long* counts_host, const RouteBufs* bufs) {
   if (!c || !in || !counts || (in->n && (!send_rec || !send_stem || !perm)))
     return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   if (n_shards < 1 || n_shards > RL_MAX_SHARDS || src_rank >= n_shards)
     return set_err(c, RL_E_INVALID, "gpu: n_shards must be 1..256 and src_rank < n_shards");
   int rc = check_sizes(c, in, 0);
@@ -773,6 +792,7 @@ int eng_route_do_limit(Engine* c, uint32_t n, const void* recv_rec, const uint8_
                        const uint64_t* src_stem_base, uint32_t n_shards, uint32_t n_rules, uint32_t rule_stride,
                        uint64_t* ret, uint64_t* stats, int isolate, void* stream) {
   if (!c || (n && !ret)) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   HIPCHK(c, hipSetDevice(c->cfg.device));
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   HIPCHK(c, hipEventRecord(c->route_ready, st));  // the received buffers are ordered on the caller's stream
@@ -790,6 +810,7 @@ int eng_fail(Engine* c, int code, const std::string& msg) { return set_err(c, co
 
 int eng_route_scatter(Engine* c, uint32_t n, const uint32_t* perm, const uint64_t* ret, rl_result* out, void* stream) {
   if (!c || !out || (n && (!perm || !ret))) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   HIPCHK(c, hipSetDevice(c->cfg.device));
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   OutDev o{out->code, out->limit_remaining, out->reset_s, (unsigned long long*)out->stats, out->status};
@@ -800,6 +821,7 @@ int eng_route_scatter(Engine* c, uint32_t n, const uint32_t* perm, const uint64_
 
 int eng_profile(Engine* c, int enable) {
   if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
+  RQ_SETTLE(c);
   HIPCHK(c, hipSetDevice(c->cfg.device));
   if (enable && !c->ev[0][0]) {
     for (uint32_t k = 0; k < PROF_RING; k++)
@@ -820,6 +842,7 @@ int eng_profile(Engine* c, int enable) {
 
 int eng_profile_read(Engine* c, double* ms, uint32_t n, uint64_t* batches) {
   if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
+  RQ_SETTLE(c);
   HIPCHK(c, hipSetDevice(c->cfg.device));
   prof_fold_all(c);
   for (uint32_t i = 0; i < n && i < RL_NUM_STAGES; i++) ms[i] = c->stage_ms[i];
@@ -862,17 +885,25 @@ void copy_time_fold(Engine* c, bool all) {
 
 int eng_synchronize(Engine* c) {
   if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
+  RQ_SETTLE(c);
   HIPCHK(c, hipSetDevice(c->cfg.device));
   HIPCHK(c, hipDeviceSynchronize());
   if (c->copy_time) copy_time_fold(c, true);
   c->seq_done = c->seq_sub;
-  return collect(c);
+  const int rc = collect(c);
+  // a packed request batch that failed in its match stage never reached the pipeline
+  const int rq = c->rq_fail;
+  c->rq_fail = 0;
+  if (rc || !rq) return rc;
+  return set_err(c, rq, c->rq_fail_msg);
 }
 
 int eng_batch_progress(Engine* c, uint64_t* submitted, uint64_t* completed) {
   if (!c || !submitted || !completed) return set_err(c, RL_E_INVALID, "gpu: null argument");
   HIPCHK(c, hipSetDevice(c->cfg.device));
-  while (c->seq_done < c->seq_sub) {
+  if (const int rc = eng_requests_advance(c, 0)) return rc;
+  // (the pending request batches, the latest rq_n submitted, have no ring event yet)
+  while (c->seq_done < c->seq_sub - c->rq_n) {
     const hipError_t e = hipEventQuery(c->done_ring[c->seq_done % PROGRESS_RING]);
     if (e == hipErrorNotReady) break;
     if (e != hipSuccess) return set_err(c, RL_E_HIP, std::string("gpu: hipEventQuery: ") + hipGetErrorString(e));
@@ -991,6 +1022,7 @@ int host_slot_run(Engine* c, HostSlot& h, const rl_batch& d, uint64_t nb, rl_res
 
 int eng_do_limit_host_async(Engine* c, const rl_batch* in, rl_result* out) {
   if (!c || !in || !out) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   const uint32_t n = in->n, nq = in->n_requests;
   if (n && (!in->stem_off || !out->code || !out->limit_remaining))
     return set_err(c, RL_E_INVALID, "gpu: null argument");
@@ -1058,6 +1090,7 @@ int eng_compact_check(Engine* c, const rl_batch_compact* in, const rl_result* ou
 int eng_do_limit_compact_async(Engine* c, const rl_batch_compact* in, rl_result* out) {
   int rc = eng_compact_check(c, in, out);
   if (rc) return rc;
+  RQ_SETTLE(c);
   const rl_config& g = c->cfg;
   const uint32_t n = in->n, nq = in->n_requests;
   const uint64_t B = in->buf_bytes;
@@ -1139,6 +1172,7 @@ int eng_do_limit_prefixed_async(Engine* c, const rl_batch_prefixed* in, rl_resul
   int rc = eng_prefixed_check(c, in, out, &T);
   if (c->host_time) c->ht[0] += wall_s() - w0;
   if (rc) return rc;
+  RQ_SETTLE(c);
   const rl_config& g = c->cfg;
   const uint32_t n = in->n, nq = in->n_requests;
   const uint64_t B = in->buf_bytes;
@@ -1197,6 +1231,7 @@ int eng_do_limit_prefixed_async(Engine* c, const rl_batch_prefixed* in, rl_resul
 
 int eng_do_limit(Engine* c, const rl_batch* in, rl_result* out) {
   if (!c || !in || !out) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   HIPCHK(c, hipSetDevice(c->cfg.device));
   BatchDev b{};
   int rc = stage(c, in, &b);
@@ -1222,6 +1257,7 @@ int eng_do_limit(Engine* c, const rl_batch* in, rl_result* out) {
 
 int eng_restore(Engine* c, const rl_restore_batch* r) {
   if (!c || !r) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   HIPCHK(c, hipSetDevice(c->cfg.device));
   if (!r->n) return RL_OK;
   // A restore batch is a batch of SET records: req = record index, hits = count,
@@ -1265,6 +1301,7 @@ int eng_restore(Engine* c, const rl_restore_batch* r) {
 
 int eng_sweep(Engine* c, int64_t now, uint64_t* n_evicted) {
   if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
+  RQ_SETTLE(c);
   if (now < 0 || now > (int64_t)NOW_MAX) return set_err(c, RL_E_TIME, "gpu: sweep time out of range");
   HIPCHK(c, hipSetDevice(c->cfg.device));
   // the sweep time becomes a floor: later requests may not be earlier
@@ -1296,6 +1333,7 @@ int eng_sweep(Engine* c, int64_t now, uint64_t* n_evicted) {
 
 int eng_table_info_get(Engine* c, rl_table_info* info) {
   if (!c || !info) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   HIPCHK(c, hipSetDevice(c->cfg.device));
   HIPCHK(c, after_batches(c, c->stream));
   HIPCHK(c, hipMemsetAsync(c->s[0].counters, 0, 32, c->stream));
@@ -1323,6 +1361,7 @@ int eng_table_info_get(Engine* c, rl_table_info* info) {
 
 int eng_debug_keys(Engine* c, const rl_batch* in, uint8_t* out_bytes, uint32_t* out_off, uint32_t out_cap) {
   if (!c || !in || !out_off) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   HIPCHK(c, hipSetDevice(c->cfg.device));
   BatchDev b{};
   int rc = stage(c, in, &b);
@@ -1360,6 +1399,7 @@ int eng_debug_keys(Engine* c, const rl_batch* in, uint8_t* out_bytes, uint32_t* 
 
 int eng_debug_log_tear(Engine* c, const rl_log_tear* arm, rl_log_tear* out) {
   if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
+  RQ_SETTLE(c);
   if (!log_tear_hook()) return set_err(c, RL_E_INVALID, "gpu: rl_debug_log_tear needs a library built with RL_LOG_TEAR");
   HIPCHK(c, hipSetDevice(c->cfg.device));
   HIPCHK(c, after_batches(c, c->stream));
@@ -1388,6 +1428,7 @@ int eng_debug_decide(Engine* c, uint32_t n, const uint32_t* before, const uint32
                     const int64_t* now, uint8_t* code, uint32_t* remaining, uint32_t* reset_s,
                     uint64_t* stat_deltas, uint8_t* lc_set) {
   if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
+  RQ_SETTLE(c);
   if (!n) return RL_OK;
   HIPCHK(c, hipSetDevice(c->cfg.device));
   for (uint32_t i = 0; i < n; i++)
@@ -1438,6 +1479,7 @@ int eng_config_load(Engine* c, const rl_config_tree* t) {
   if (!c || !t || (t->n_nodes && (!t->nodes || (t->key_bytes_len && !t->key_bytes))) ||
       (t->cache_key_prefix_len && !t->cache_key_prefix))
     return set_err(c, RL_E_INVALID, "gpu: null config tree");
+  RQ_SETTLE(c);
   HIPCHK(c, hipSetDevice(c->cfg.device));
   const uint32_t n = t->n_nodes;
   std::vector<CfgNode> nodes(n);
@@ -1536,6 +1578,7 @@ hipError_t verdict_d2h(const uint8_t* block, uint32_t nq, rl_request_verdict* v,
 int eng_do_limit_requests(Engine* c, const rl_request_batch* in, rl_request_result* out, RequestsDoLimit run,
                           void* user, uint32_t opts, rl_request_verdict* verdict) {
   if (!c || !in || (!out && !verdict)) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   if (verdict && in->n_requests && !verdict->overall_code)
     return set_err(c, RL_E_INVALID, "gpu: rl_request_verdict without overall_code");
   if (verdict && (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW)) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
@@ -1706,10 +1749,342 @@ int eng_do_limit_requests(Engine* c, const rl_request_batch* in, rl_request_resu
   return RL_OK;
 }
 
+// ---- packed request batches, pipelined (rl_do_limit_requests_packed_async) --
+
+// The host checks only what the copy and the unpack's bounds rely on: sections
+// inside buf, the index's first entry zero and its last the batch's sizes;
+// every tile's own entry and the override list are checked on the device.
+int eng_requests_packed_check(Engine* c, const rl_request_batch_packed* in, const rl_request_result* out, uint32_t opts,
+                              const rl_request_verdict* verdict, uint32_t* tiles) {
+  if (!c || !in || (!out && !verdict)) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
+  if (!c->cfg_loaded) return set_err(c, RL_E_INVALID, "gpu: no rate limit configuration loaded");
+  const rl_config& g = c->cfg;
+  const uint32_t n = in->n_descriptors, nq = in->n_requests, ne = in->n_entries;
+  if (n > g.max_batch || nq > g.max_requests || in->n_rules > g.max_rules)
+    return set_err(c, RL_E_CAPACITY, "gpu: request batch exceeds configured max_batch/max_requests/max_rules");
+  if (n && !nq) return set_err(c, RL_E_INVALID, "gpu: descriptors without requests");
+  if (in->reserved) return set_err(c, RL_E_INVALID, "gpu: packed request batch: reserved field not zero");
+  if (in->n_overrides > n) return set_err(c, RL_E_INVALID, "gpu: packed request batch: more overrides than descriptors");
+  const uint32_t T = (nq + RL_REQUESTS_TILE - 1) / RL_REQUESTS_TILE;
+  *tiles = T;
+  const uint64_t B = in->buf_bytes;
+  if (!in->buf) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  auto sect = [&](uint64_t off, uint64_t bytes) { return off % 4 == 0 && off <= B && bytes <= B - off; };
+  if (!sect(in->index, 16ull * (T + 1)) || !sect(in->req, nq * 4ull) || !sect(in->now, nq * 4ull) ||
+      !sect(in->hits, nq * 4ull) || !sect(in->desc, n * 2ull) || !sect(in->key_len, ne * 2ull) ||
+      !sect(in->value_len, ne * 2ull) || !sect(in->overrides, in->n_overrides * (uint64_t)sizeof(rl_request_override)) ||
+      !sect(in->domain_bytes, 0) || !sect(in->entry_bytes, 0))
+    return set_err(c, RL_E_INVALID, "gpu: packed request batch section outside buf or not 4-byte aligned");
+  const uint32_t* ix = reinterpret_cast<const uint32_t*>(in->buf + in->index);
+  const uint32_t* tot = ix + 4ull * T;
+  if (ix[0] || ix[1] || ix[2] || ix[3] || tot[0] != n || tot[1] != ne)
+    return set_err(c, RL_E_INVALID, "gpu: packed request batch index does not start at zero or end at the batch's sizes");
+  if (tot[3] > g.max_stem_bytes) return set_err(c, RL_E_CAPACITY, "gpu: request batch's entry bytes exceed max_stem_bytes");
+  if (!sect(in->domain_bytes, tot[2]) || !sect(in->entry_bytes, tot[3]))
+    return set_err(c, RL_E_INVALID, "gpu: packed request batch domain or entry bytes outside buf");
+  return RL_OK;
+}
+
+namespace {
+
+void free_request_slots(Engine* c) {
+  if (!c->rq) return;
+  for (uint32_t j = 0; j < RL_REQUESTS_INFLIGHT; j++) {
+    RequestSlot& s = c->rq[j];
+    HostSlot& h = s.h;
+    void* bufs[] = {h.stem, h.off, h.req, h.limit, h.hits, h.rule, h.now, h.unit, h.flags, h.code, h.rem,
+                    h.reset, h.stats, h.cbuf, s.mbuf};
+    for (void* p : bufs)
+      if (p) (void)hipFree(p);
+    if (s.h_cnt) (void)hipHostFree(s.h_cnt);
+    if (s.count_done) (void)hipEventDestroy(s.count_done);
+    if (h.in_done) (void)hipEventDestroy(h.in_done);
+  }
+  if (c->rq_copy) (void)hipStreamDestroy(c->rq_copy);
+  c->rq_copy = nullptr;
+  delete[] c->rq;
+  c->rq = nullptr;
+  c->rq_head = c->rq_n = 0;
+}
+
+int ensure_request_slots(Engine* c) {
+  if (c->rq) return RL_OK;
+  const rl_config& g = c->cfg;
+  c->rq = new RequestSlot[RL_REQUESTS_INFLIGHT];
+  bool ok = rl_stream_create(&c->rq_copy, SR_HOSTCOPY) == hipSuccess;
+  for (uint32_t j = 0; j < RL_REQUESTS_INFLIGHT; j++) {
+    RequestSlot& s = c->rq[j];
+    HostSlot& h = s.h;
+    s.st = c->pipe[j % NBUF];
+    ok = ok && dalloc(&h.stem, (size_t)g.max_stem_bytes + 64) == hipSuccess &&
+         dalloc(&h.off, (size_t)g.max_batch + 1) == hipSuccess && dalloc(&h.req, g.max_batch) == hipSuccess &&
+         dalloc(&h.limit, g.max_batch) == hipSuccess && dalloc(&h.hits, g.max_batch) == hipSuccess &&
+         dalloc(&h.rule, g.max_batch) == hipSuccess && dalloc(&h.now, g.max_requests) == hipSuccess &&
+         dalloc(&h.unit, g.max_batch) == hipSuccess && dalloc(&h.flags, g.max_batch) == hipSuccess &&
+         dalloc(&h.code, g.max_batch) == hipSuccess && dalloc(&h.rem, g.max_batch) == hipSuccess &&
+         dalloc(&h.reset, g.max_batch) == hipSuccess &&
+         dalloc(&h.stats, (size_t)g.max_rules * RL_NUM_STATS) == hipSuccess &&
+         hipHostMalloc((void**)&s.h_cnt, 16, hipHostMallocDefault) == hipSuccess &&
+         hipEventCreateWithFlags(&s.count_done, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&h.in_done, hipEventDisableTiming) == hipSuccess;
+  }
+  if (!ok) {
+    free_request_slots(c);
+    return set_err(c, RL_E_HIP, "gpu: request slot allocation failed");
+  }
+  return RL_OK;
+}
+
+// Device arrays into the caller's host arrays on `st`, ToHost's capacity at a time.
+struct ToHostList {
+  ToHost th{};
+  hipStream_t st;
+  hipError_t e = hipSuccess;
+  explicit ToHostList(hipStream_t s) : st(s) {}
+  void flush() {
+    if (th.n && e == hipSuccess) e = copy_to_host(th, st);
+    th.n = 0;
+  }
+  void add(void* dst, const void* src, uint64_t bytes) {
+    if (!dst || !bytes) return;
+    if (th.n == TO_HOST_MAX) flush();
+    th.dst[th.n] = (uint8_t*)dst;
+    th.src[th.n] = (const uint8_t*)src;
+    th.bytes[th.n++] = bytes;
+  }
+};
+
+// The second half of the batch in slot s, whose count has arrived.
+int request_second_half(Engine* c, RequestSlot& s) {
+  HostSlot& h = s.h;
+  const uint32_t n = s.n, nq = s.nq, bits = s.h_cnt[2];
+  const uint64_t seq = s.seq;
+  if (bits) {
+    // failed in the match stage: no second half, the table untouched; its
+    // place in the progress ring completes with the work before it
+    if (!c->rq_fail) {
+      if (bits & MATCH_ERR_UNPACK) {
+        c->rq_fail = RL_E_INVALID;
+        c->rq_fail_msg = "gpu: malformed packed request batch (tile index or override list)";
+      } else if (bits & MATCH_ERR_REQ) {
+        c->rq_fail = RL_E_INVALID;
+        c->rq_fail_msg = "gpu: malformed request batch (request index or entry byte layout)";
+      } else {
+        c->rq_fail = RL_E_CAPACITY;
+        c->rq_fail_msg = "gpu: matched stems exceed max_stem_bytes";
+      }
+    }
+    HIPCHK(c, hipEventRecord(c->done_ring[seq % PROGRESS_RING], s.st));
+    return RL_OK;
+  }
+  const uint32_t nm = n ? s.h_cnt[0] : 0;
+  hipStream_t a = c->pipe[c->next];  // (the count is on the host: the first half is complete, nothing to wait for)
+  if (!n) HIPCHK(c, hipMemsetAsync(h.off, 0, 4, a));  // off[0] of the empty batch
+  rl_batch pb{};
+  pb.n = nm;
+  pb.n_requests = nq;
+  pb.n_rules = s.n_rules;
+  pb.stem_bytes = h.stem;
+  pb.stem_off = h.off;
+  pb.now = h.now;
+  pb.req_idx = h.req;
+  pb.unit = h.unit;
+  pb.flags = h.flags;
+  pb.limit = h.limit;
+  pb.hits = h.hits;
+  pb.rule_id = h.rule;
+  BatchDev b = dev_view(c, &pb, c->cfg.max_stem_bytes);
+  OutDev o{h.code, h.rem, h.reset, s.n_rules ? h.stats : nullptr, nullptr};
+  const uint32_t k = enqueue(c, b, o, 0, nullptr, true);
+  a = c->pipe[k];
+  s.st = a;
+  launch_match_expand(s.r, s.m, h.code, h.rem, h.reset, s.ro, a);
+  HIPCHK(c, hipGetLastError());
+  if (s.has_verdict && nq) {
+    const VerdictDev vd = verdict_view(nq, n, s.opts, s.r.req, s.ro.match, s.ro.code, s.ro.rem, s.ro.reset, s.ro.rpu,
+                                       s.vblock);
+    HIPCHK(c, launch_verdict(vd, s.vblock, a));
+  }
+  ToHostList th(a);
+  if (s.has_out) {
+    const rl_request_result& out = s.out;
+    th.add(out.code, s.ro.code, n);
+    th.add(out.limit_remaining, s.ro.rem, n * 4ull);
+    th.add(out.reset_s, s.ro.reset, n * 4ull);
+    th.add(out.match, s.ro.match, n);
+    th.add(out.rule_id, s.ro.rule, n * 4ull);
+    th.add(out.requests_per_unit, s.ro.rpu, n * 4ull);
+    th.add(out.unit, s.ro.unit, n);
+    if (s.n_rules) th.add(out.stats, h.stats, (size_t)s.n_rules * RL_NUM_STATS * 8);
+  }
+  if (s.has_verdict && nq) {
+    const VerdictLayout L = verdict_layout(nq);
+    const rl_request_verdict& v = s.verdict;
+    th.add(v.overall_code, s.vblock + L.o_code, nq);
+    th.add(v.flags, s.vblock + L.o_flags, nq);
+    th.add(v.min_descriptor, s.vblock + L.o_min, nq * 4ull);
+    th.add(v.header_limit, s.vblock + L.o_limit, nq * 4ull);
+    th.add(v.header_remaining, s.vblock + L.o_rem, nq * 4ull);
+    th.add(v.header_reset_s, s.vblock + L.o_reset, nq * 4ull);
+    th.add(v.global_shadow, s.vblock + L.shadow, 8);
+  }
+  th.flush();
+  HIPCHK(c, th.e);
+  HIPCHK(c, hipEventRecord(c->done_ring[seq % PROGRESS_RING], a));
+  HIPCHK(c, hipGetLastError());
+  c->batches++;
+  c->decisions += nm;
+  return RL_OK;
+}
+
+}  // namespace
+
+int eng_requests_advance(Engine* c, uint32_t must) {
+  if (!c->rq_n) return RL_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  while (c->rq_n) {
+    RequestSlot& s = c->rq[c->rq_head];
+    if (must) {
+      HIPCHK(c, hipEventSynchronize(s.count_done));
+      must--;
+    } else {
+      const hipError_t e = hipEventQuery(s.count_done);
+      if (e == hipErrorNotReady) break;
+      HIPCHK(c, e);
+    }
+    c->rq_head = (c->rq_head + 1) % RL_REQUESTS_INFLIGHT;
+    c->rq_n--;
+    const int rc = request_second_half(c, s);
+    if (rc) return rc;
+  }
+  return RL_OK;
+}
+
+int eng_do_limit_requests_packed_async(Engine* c, const rl_request_batch_packed* in, rl_request_result* out,
+                                       uint32_t opts, rl_request_verdict* verdict) {
+  uint32_t T = 0;
+  int rc = eng_requests_packed_check(c, in, out, opts, verdict, &T);
+  if (rc) return rc;
+  const uint32_t n = in->n_descriptors, nq = in->n_requests, ne = in->n_entries, nov = in->n_overrides;
+  const uint64_t B = in->buf_bytes;
+  const uint32_t* tot = reinterpret_cast<const uint32_t*>(in->buf + in->index) + 4ull * T;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if ((rc = ensure_request_slots(c))) return rc;
+  // the oldest batches whose count has arrived; a full ring waits for the oldest one's
+  if ((rc = eng_requests_advance(c, c->rq_n == RL_REQUESTS_INFLIGHT ? 1 : 0))) return rc;
+  RequestSlot& s = c->rq[(c->rq_head + c->rq_n) % RL_REQUESTS_INFLIGHT];
+  HostSlot& h = s.h;
+  hipStream_t st = s.st;  // (after the slot's previous batch, in stream order)
+  // the slot's carved buffer (256-B aligned pieces) and its copy of buf grow to the largest batch seen
+  const size_t scan = n ? match_scan_bytes(n) : 0;
+  size_t need = 0;
+  auto piece = [&need](size_t bytes) {
+    const size_t o = need;
+    need += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
+    return o;
+  };
+  const size_t o_domoff = piece((nq + 1) * 4ull), o_req = piece(n * 4ull), o_ent = piece((n + 1) * 4ull),
+               o_doff = piece((n + 1) * 4ull), o_ov = piece(nov ? n * 10ull : 0), o_v = piece(n * 16ull),
+               o_kind = piece(n * 4ull), o_rpu = piece(n * 4ull), o_rule = piece(n * 4ull), o_cnt = piece(16),
+               o_code = piece(n), o_rem = piece(n * 4ull), o_reset = piece(n * 4ull), o_match = piece(n),
+               o_orule = piece(n * 4ull), o_orpu = piece(n * 4ull), o_ounit = piece(n), o_tmp = piece(scan);
+  const size_t o_verdict = verdict ? piece(verdict_layout(nq).bytes) : 0;
+  if (need > s.mbuf_cap || B > h.cbuf_cap) HIPCHK(c, hipStreamSynchronize(st));  // the slot's previous batch
+  if (need > s.mbuf_cap) {
+    if (s.mbuf) HIPCHK(c, hipFree(s.mbuf));
+    s.mbuf = nullptr;
+    s.mbuf_cap = 0;
+    HIPCHK(c, hipMalloc((void**)&s.mbuf, need));
+    s.mbuf_cap = need;
+  }
+  if (B > h.cbuf_cap) {
+    if (h.cbuf) HIPCHK(c, hipFree(h.cbuf));
+    h.cbuf = nullptr;
+    h.cbuf_cap = 0;
+    HIPCHK(c, dalloc(&h.cbuf, B + 64));
+    h.cbuf_cap = B;
+  }
+  // progress: submitted now, complete when its second half is (its ring event is recorded then)
+  if (c->seq_sub - c->seq_done >= PROGRESS_RING) {
+    HIPCHK(c, hipEventSynchronize(c->done_ring[c->seq_done % PROGRESS_RING]));
+    c->seq_done++;
+  }
+  uint8_t* M = s.mbuf;
+  // The copy goes on a stream of its own: the slot's stream still runs its previous batch's second half,
+  // which reads nothing of cbuf (the first half did, and its count has arrived), and the batches' copies
+  // then follow each other on the link without waiting for any kernel.
+  if (B) {
+    HIPCHK(c, hipMemcpyAsync(h.cbuf, in->buf, B, hipMemcpyHostToDevice, c->rq_copy));
+    HIPCHK(c, hipEventRecord(h.in_done, c->rq_copy));
+    HIPCHK(c, hipStreamWaitEvent(st, h.in_done, 0));
+  }
+  HIPCHK(c, hipMemsetAsync(M + o_cnt, 0, 16, st));
+  if (nov) HIPCHK(c, hipMemsetAsync(M + o_ov, 0, n * 10ull, st));
+  // the dense override arrays: rpu and rule (4-byte aligned: n x 4 each), then flags and units
+  uint32_t* ov_rpu = (uint32_t*)(M + o_ov);
+  uint32_t* ov_rule = ov_rpu + n;
+  uint8_t* ovf = (uint8_t*)(ov_rule + n);
+  uint8_t* ov_unit = ovf + n;
+  MatchBuf m{(unsigned long long*)(M + o_v), (uint32_t*)(M + o_kind), (uint32_t*)(M + o_rpu),
+             (uint32_t*)(M + o_rule), (uint32_t*)(M + o_cnt)};
+  launch_unpack_requests(*in, h.cbuf, (uint32_t*)(M + o_domoff), h.now, (uint32_t*)(M + o_req),
+                         (uint32_t*)(M + o_ent), (uint32_t*)(M + o_doff), ovf, ov_rpu, ov_unit, ov_rule, m.count + 2, st);
+  ReqDev r;
+  r.n_req = nq;
+  r.n_desc = n;
+  r.n_ent = ne;
+  r.dom_total = tot[2];
+  r.desc_total = tot[3];
+  r.dom = h.cbuf + in->domain_bytes;
+  r.dom_off = (const uint32_t*)(M + o_domoff);
+  r.hits = (const uint32_t*)(h.cbuf + in->hits);
+  r.req = (const uint32_t*)(M + o_req);
+  r.ent_first = (const uint32_t*)(M + o_ent);
+  r.desc_off = (const uint32_t*)(M + o_doff);
+  r.desc = h.cbuf + in->entry_bytes;
+  r.klen = (const uint16_t*)(h.cbuf + in->key_len);
+  r.vlen = (const uint16_t*)(h.cbuf + in->value_len);
+  r.ovf = nov ? ovf : nullptr;
+  r.ov_rpu = nov ? ov_rpu : nullptr;
+  r.ov_unit = nov ? ov_unit : nullptr;
+  r.ov_rule = nov ? ov_rule : nullptr;
+  // the matched descriptors become an ordinary DoLimit batch in the slot's staging
+  PackOut po{h.stem, h.off, h.req, h.unit, h.flags, h.limit, h.hits, h.rule, c->cfg.max_stem_bytes};
+  launch_match(c->cfg_dev, r, m, po, M + o_tmp, scan, st);
+  HIPCHK(c, hipGetLastError());
+  // (by a kernel's stores: a DMA copy back would queue behind the next batch's input copy)
+  ToHost th{};
+  th.src[0] = M + o_cnt;
+  th.dst[0] = (uint8_t*)s.h_cnt;
+  th.bytes[0] = 16;
+  th.n = 1;
+  HIPCHK(c, copy_to_host(th, st));
+  HIPCHK(c, hipEventRecord(s.count_done, st));
+  s.n = n;
+  s.nq = nq;
+  s.n_rules = in->n_rules;
+  s.opts = opts;
+  s.seq = c->seq_sub++;
+  s.r = r;
+  s.m = m;
+  s.ro = ReqOutDev{M + o_code, (uint32_t*)(M + o_rem), (uint32_t*)(M + o_reset), M + o_match,
+                   (uint32_t*)(M + o_orule), (uint32_t*)(M + o_orpu), M + o_ounit};
+  s.vblock = verdict ? M + o_verdict : nullptr;
+  s.has_out = out != nullptr;
+  s.has_verdict = verdict != nullptr;
+  if (out) s.out = *out;
+  if (verdict) s.verdict = *verdict;
+  if (verdict && !nq && verdict->global_shadow) *verdict->global_shadow = 0;
+  c->rq_n++;
+  return RL_OK;
+}
+
 int eng_debug_verdict(Engine* c, uint32_t nq, uint32_t n, const uint32_t* req_idx, const uint8_t* match,
                       const uint8_t* code, const uint32_t* limit_remaining, const uint32_t* reset_s,
                       const uint32_t* requests_per_unit, uint32_t opts, rl_request_verdict* verdict) {
   if (!c || !verdict) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   if (nq && !verdict->overall_code) return set_err(c, RL_E_INVALID, "gpu: rl_request_verdict without overall_code");
   if (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
   if (n > c->cfg.max_batch || nq > c->cfg.max_requests)
@@ -1767,6 +2142,7 @@ int eng_debug_verdict(Engine* c, uint32_t nq, uint32_t n, const uint32_t* req_id
 
 int eng_local_cache_info_get(Engine* c, int64_t now, rl_local_cache_info* info) {
   if (!c || !info) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   if (now < 0 || now > (int64_t)NOW_MAX) return set_err(c, RL_E_TIME, "gpu: now out of range");
   HIPCHK(c, hipSetDevice(c->cfg.device));
   HIPCHK(c, after_batches(c, c->stream));
@@ -1838,6 +2214,7 @@ bool slots_valid(const Slot* s, uint64_t n, uint64_t arena_used16) {
 
 int eng_snapshot_size(Engine* c, uint64_t* bytes) {
   if (!c || !bytes) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   SnapHeader h{};
   std::vector<unsigned long long> ctr;
   int rc = snap_state(c, &h, ctr);
@@ -1848,6 +2225,7 @@ int eng_snapshot_size(Engine* c, uint64_t* bytes) {
 
 int eng_snapshot_save(Engine* c, void* host, uint64_t bytes) {
   if (!c || !host) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   SnapHeader h{};
   std::vector<unsigned long long> ctr;
   int rc = snap_state(c, &h, ctr);
@@ -1876,6 +2254,7 @@ int eng_snapshot_save(Engine* c, void* host, uint64_t bytes) {
 
 int eng_snapshot_load(Engine* c, const void* host, uint64_t bytes) {
   if (!c || !host) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   SnapHeader h;
   if (bytes < sizeof h) return set_err(c, RL_E_INVALID, "gpu: snapshot too short");
   memcpy(&h, host, sizeof h);
@@ -1934,6 +2313,7 @@ struct DevBufs {
 
 int eng_export_range(Engine* c, uint64_t s0, uint64_t s1, rl_records* out, rl_export_info* info) {
   if (!c || !info) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
   if (out && (!out->stem_off || (out->n && (!out->unit || !out->flags || !out->ws || !out->count || !out->expire ||
                                             !out->lc)) ||
               (out->stem_cap && !out->stem_bytes)))
@@ -2024,6 +2404,7 @@ int eng_import_check(Engine* c, const rl_records* in) {
 
 int eng_import(Engine* c, const rl_records* in) {
   if (const int rc = eng_import_check(c, in)) return rc;
+  RQ_SETTLE(c);
   const uint32_t n = in->n;
   if (!n) return RL_OK;
   // group the records by stem (a stem's records stay in arrival order): one
@@ -2114,6 +2495,7 @@ int eng_lookup_check(Engine* c, const rl_keys* in, const rl_key_state* out) {
 
 int eng_lookup(Engine* c, const rl_keys* in, rl_key_state* out) {
   if (const int rc = eng_lookup_check(c, in, out)) return rc;
+  RQ_SETTLE(c);
   const uint32_t n = in->n;
   if (!n) return RL_OK;
   const uint32_t nb = in->stem_off[n];

@@ -134,6 +134,7 @@ inline VerdictLayout verdict_layout(uint32_t nq) {
 }
 
 constexpr uint32_t MATCH_ERR_REQ = 1, MATCH_ERR_CAP = 2;
+constexpr uint32_t MATCH_ERR_UNPACK = 4;  // k_unpack_requests: an index entry or override that does not match the batch
 
 __host__ __device__ inline uint64_t cfg_hash(int32_t parent, const uint8_t* p, uint32_t len) {
   uint64_t h = 0xcbf29ce484222325ull ^ ((uint64_t)(uint32_t)(parent + 1) * 0x9E3779B97F4A7C15ull);
@@ -154,6 +155,16 @@ void launch_match(const CfgDev& cfg, const ReqDev& r, const MatchBuf& m, const P
                   size_t tmp_bytes, hipStream_t st);
 void launch_match_expand(const ReqDev& r, const MatchBuf& m, const uint8_t* code, const uint32_t* rem,
                          const uint32_t* reset, const ReqOutDev& out, hipStream_t st);
+// A one-buffer request batch (rl_request_batch_packed; buf = the device copy
+// of its buffer) -> the arrays of ReqDev that do not cross the link: dom_off
+// [nq + 1], req [n], ent_first and desc_off [n + 1], the 64-bit clocks, and
+// the dense override arrays scattered from the sparse list (zeroed by the
+// caller on the stream when n_overrides != 0, else unused). The totals come
+// from the host buffer's last index entry (already checked against the batch's
+// sizes). A tile or override that does not match sets MATCH_ERR_UNPACK in *err.
+void launch_unpack_requests(const rl_request_batch_packed& pb, const uint8_t* buf, uint32_t* dom_off, int64_t* now,
+                            uint32_t* req, uint32_t* ent_first, uint32_t* desc_off, uint8_t* ovf, uint32_t* ov_rpu,
+                            uint8_t* ov_unit, uint32_t* ov_rule, uint32_t* err, hipStream_t st);
 // Enqueue the verdict over per-descriptor answers already on the device
 // (v.req non-decreasing and < v.n_req): zeroes the accumulators at `block`
 // (verdict_layout(v.n_req), whose pointers v holds), then k_verdict and

@@ -375,7 +375,200 @@ __global__ __launch_bounds__(256) void k_verdict_final(VerdictDev v) {
   if ((threadIdx.x & 63u) == 0 && b) atomicAdd(v.shadow, (unsigned long long)__popcll(b));
 }
 
+// ---- k_unpack_requests: a one-buffer request batch (rl_request_batch_packed)
+// -> the offset arrays ReqDev reads (dom_off, req, ent_first, desc_off), the
+// 64-bit clocks and the dense override arrays; lengths and bytes stay where
+// the copy put them. Workgroups [0, tiles): one per tile of RQ_TILE requests,
+// one lane per request, following k_unpack_prefixed: the tile's index entry
+// gives its first descriptor, entry, domain byte and entry byte, so tiles are
+// independent. The entry against the next one, the totals and the tile's own
+// descriptor and domain-byte sums is checked before anything is written; the
+// entry and entry-byte sums accumulate over the descriptor chunks, every lane
+// bounded by the tile's checked end, and are compared at the end. Every store
+// lands at a descriptor index in [I0.x, I1.x] or a request index of the tile,
+// inside arrays of n + 1 and nq + 1 elements (the totals are host-checked), so
+// a malformed tile fails the batch (MATCH_ERR_UNPACK) and never writes outside
+// it. Workgroups from `tiles` on: one lane per override of the sparse list,
+// scattered into the dense arrays (zeroed on the stream before the launch).
+constexpr uint32_t RQ_TILE = RL_REQUESTS_TILE;
+static_assert(RQ_TILE == 256, "k_unpack_requests: one lane per request of a tile");
+
+// 256 lanes: wave-level inclusive scans by shuffles, then across the 4 waves.
+template <typename T>
+__device__ inline T block_excl_scan(T v, T* tmp, T* total) {
+  const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  T x = v;
+#pragma unroll
+  for (uint32_t o = 1; o < 64; o <<= 1) {
+    const T y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) tmp[wv] = x;
+  __syncthreads();
+  T base = 0;
+  for (uint32_t k = 0; k < wv; k++) base += tmp[k];
+  *total = tmp[0] + tmp[1] + tmp[2] + tmp[3];
+  __syncthreads();
+  return base + x - v;
+}
+
+struct UnpackReq {
+  uint32_t nq, n, tiles, n_ov;
+  uint4 tot;  // {n, n_ent, domain bytes, entry bytes}: the index's last entry, host-checked
+  const uint32_t* reqw;
+  const uint32_t* now32;
+  const uint16_t* descw;
+  const uint16_t* klen;
+  const uint16_t* vlen;
+  const uint32_t* index;
+  const rl_request_override* ov;
+  uint32_t* dom_off;
+  int64_t* now;
+  uint32_t* req;
+  uint32_t* ent_first;
+  uint32_t* desc_off;
+  uint8_t* ovf;
+  uint32_t* ov_rpu;
+  uint8_t* ov_unit;
+  uint32_t* ov_rule;
+  uint32_t* err;  // MatchBuf::count + 2
+};
+
+__global__ __launch_bounds__(256) void k_unpack_requests(UnpackReq u) {
+  __shared__ uint32_t s_tmp[3][4];
+  __shared__ unsigned long long s_tmp64[4];
+  __shared__ uint32_t s_first[RQ_TILE + 1];
+  const uint32_t tid = threadIdx.x;
+  if (blockIdx.x >= u.tiles) {  // the overrides
+    const uint32_t i = (blockIdx.x - u.tiles) * 256 + tid;
+    if (i >= u.n_ov) return;
+    const rl_request_override o = u.ov[i];
+    const bool bad = o.descriptor >= u.n || (i && u.ov[i - 1].descriptor >= o.descriptor) ||
+                     (o.reserved[0] | o.reserved[1] | o.reserved[2]) != 0;
+    if (bad) {
+      atomicOr(u.err, MATCH_ERR_UNPACK);
+      return;
+    }
+    u.ovf[o.descriptor] = 1;
+    u.ov_rpu[o.descriptor] = o.requests_per_unit;
+    u.ov_unit[o.descriptor] = o.unit;
+    u.ov_rule[o.descriptor] = o.rule_id;
+    return;
+  }
+  const uint32_t t = blockIdx.x, q0 = t * RQ_TILE, q = q0 + tid;
+  const uint32_t* ix = u.index + 4ull * t;  // (a section is 4-byte aligned only)
+  const uint4 I0 = make_uint4(ix[0], ix[1], ix[2], ix[3]), I1 = make_uint4(ix[4], ix[5], ix[6], ix[7]);
+  const uint32_t rw = q < u.nq ? u.reqw[q] : 0u;
+  const uint32_t nd = rw & 0xFFFFu, dl = rw >> 16;
+  uint32_t T_nd, T_dl;
+  const uint32_t e_nd = block_excl_scan(nd, s_tmp[0], &T_nd);
+  const uint32_t e_dl = block_excl_scan(dl, s_tmp[1], &T_dl);
+  // the tile's entry against its own sums and the totals (uniform per block)
+  const bool ok = I0.x <= I1.x && I0.y <= I1.y && I0.z <= I1.z && I0.w <= I1.w && I1.x <= u.tot.x &&
+                  I1.y <= u.tot.y && I1.z <= u.tot.z && I1.w <= u.tot.w && I1.x - I0.x == T_nd && I1.z - I0.z == T_dl;
+  if (!ok) {
+    if (tid == 0) atomicOr(u.err, MATCH_ERR_UNPACK);
+    return;
+  }
+  s_first[tid] = I0.x + e_nd;
+  if (tid == 0) s_first[RQ_TILE] = I1.x;
+  if (q < u.nq) {
+    u.now[q] = u.now32[q];
+    u.dom_off[q] = I0.z + e_dl;
+  }
+  if (tid == 0) u.dom_off[min(q0 + RQ_TILE, u.nq)] = I1.z;  // (the next tile writes the same value)
+  __syncthreads();
+  // descriptors of the tile, 256 at a time: entry and byte offsets by block scans
+  const uint32_t D = T_nd, E1 = I1.y;
+  const unsigned long long span = I1.w - I0.w;
+  uint32_t bad = 0;
+  unsigned long long carry_e = 0, carry_b = 0;
+  for (uint32_t c = 0; c < D; c += 256) {
+    const uint32_t j = c + tid, d = I0.x + j;
+    uint32_t ne = 0;
+    if (j < D) {
+      ne = u.descw[d];
+      // request of descriptor d: the last tile request whose first descriptor <= d
+      uint32_t lo = 0, hi = RQ_TILE;  // s_first[lo] <= d < s_first[hi]
+      while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (s_first[mid] <= d) lo = mid;
+        else hi = mid;
+      }
+      u.req[d] = q0 + lo;
+    }
+    uint32_t T_e;
+    const uint32_t e_e = block_excl_scan(ne, s_tmp[2], &T_e);
+    const unsigned long long ef64 = (unsigned long long)I0.y + carry_e + e_e;
+    const uint32_t ef = (uint32_t)ef64;
+    unsigned long long bl = 0;
+    if (j < D) {
+      if (ef64 + ne > E1) {  // (past the tile's checked end)
+        bad = 1;
+      } else {
+        for (uint32_t e = ef; e < ef + ne; e++) bl += (unsigned long long)u.klen[e] + u.vlen[e] + 2u;
+        if (bl > span) {
+          bad = 1;
+          bl = 0;
+        }
+      }
+    }
+    unsigned long long T_b;
+    const unsigned long long e_b = block_excl_scan(bl, s_tmp64, &T_b);  // (256 x span < 2^40)
+    if (j < D) {
+      const unsigned long long bo = carry_b + e_b;
+      if (bad || bo + bl > span) {
+        bad = 1;
+        u.ent_first[d] = I0.y;
+        u.desc_off[d] = I0.w;
+      } else {
+        u.ent_first[d] = ef;
+        u.desc_off[d] = I0.w + (uint32_t)bo;
+      }
+    }
+    carry_e += T_e;
+    carry_b += T_b;
+  }
+  if (tid == 0) {
+    if (carry_e != I1.y - I0.y || carry_b != span) bad = 1;
+    u.ent_first[I1.x] = I1.y;  // (the next tile writes the same values as its first offsets)
+    u.desc_off[I1.x] = I1.w;
+  }
+  if (bad) atomicOr(u.err, MATCH_ERR_UNPACK);
+}
+
 }  // namespace
+
+void launch_unpack_requests(const rl_request_batch_packed& pb, const uint8_t* buf, uint32_t* dom_off, int64_t* now,
+                            uint32_t* req, uint32_t* ent_first, uint32_t* desc_off, uint8_t* ovf, uint32_t* ov_rpu,
+                            uint8_t* ov_unit, uint32_t* ov_rule, uint32_t* err, hipStream_t st) {
+  UnpackReq u;
+  u.nq = pb.n_requests;
+  u.n = pb.n_descriptors;
+  u.tiles = (pb.n_requests + RQ_TILE - 1) / RQ_TILE;
+  u.n_ov = pb.n_overrides;
+  const uint32_t* host_tot = reinterpret_cast<const uint32_t*>(pb.buf + pb.index) + 4ull * u.tiles;
+  u.tot = make_uint4(host_tot[0], host_tot[1], host_tot[2], host_tot[3]);
+  u.reqw = reinterpret_cast<const uint32_t*>(buf + pb.req);
+  u.now32 = reinterpret_cast<const uint32_t*>(buf + pb.now);
+  u.descw = reinterpret_cast<const uint16_t*>(buf + pb.desc);
+  u.klen = reinterpret_cast<const uint16_t*>(buf + pb.key_len);
+  u.vlen = reinterpret_cast<const uint16_t*>(buf + pb.value_len);
+  u.index = reinterpret_cast<const uint32_t*>(buf + pb.index);
+  u.ov = reinterpret_cast<const rl_request_override*>(buf + pb.overrides);
+  u.dom_off = dom_off;
+  u.now = now;
+  u.req = req;
+  u.ent_first = ent_first;
+  u.desc_off = desc_off;
+  u.ovf = ovf;
+  u.ov_rpu = ov_rpu;
+  u.ov_unit = ov_unit;
+  u.ov_rule = ov_rule;
+  u.err = err;
+  const uint32_t g = u.tiles + (u.n_ov + 255) / 256;
+  if (g) k_unpack_requests<<<g, 256, 0, st>>>(u);
+}
 
 VerdictDev verdict_view(uint32_t n_req, uint32_t n_desc, uint32_t opts, const uint32_t* req, const uint8_t* match,
                         const uint8_t* code, const uint32_t* rem, const uint32_t* reset, const uint32_t* rpu,

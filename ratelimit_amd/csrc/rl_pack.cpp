@@ -364,4 +364,115 @@ int rl_packer_pack(rl_packer* k, const uint8_t* msgs, const uint64_t* msg_off, u
   return RL_OK;
 }
 
+// rl_request_batch -> the one-buffer layout of rl_request_batch_packed. Two
+// passes: the first only reads and checks (so a refused batch leaves buf as
+// it was), the second writes the sections and the tile index.
+int rl_request_batch_pack(const rl_request_batch* in, uint8_t* buf, uint64_t buf_cap, rl_request_batch_packed* out) {
+  if (!in || !out) return RL_E_INVALID;
+  const uint32_t nq = in->n_requests, n = in->n_descriptors, ne = in->n_entries;
+  if (!in->domain_off || !in->entry_first || !in->desc_off || (nq && (!in->now || !in->hits)) ||
+      (n && (!in->req_idx || !nq)) || (ne && (!in->key_len || !in->value_len)))
+    return RL_E_INVALID;
+  if (in->override_flags && (!in->override_rpu || !in->override_unit || !in->override_rule)) return RL_E_INVALID;
+  if (in->domain_off[0] || in->entry_first[0] || in->desc_off[0] || in->entry_first[n] != ne) return RL_E_INVALID;
+  for (uint32_t q = 0; q < nq; q++) {
+    if (in->domain_off[q + 1] < in->domain_off[q] || in->domain_off[q + 1] - in->domain_off[q] > 65535u)
+      return RL_E_INVALID;
+    if (in->now[q] < 0 || in->now[q] > (int64_t)0xFFFFFFFFll) return RL_E_INVALID;
+  }
+  uint32_t nov = 0;
+  for (uint32_t d = 0, run = 0; d < n; d++) {
+    const uint32_t q = in->req_idx[d];
+    if (q >= nq || (d && q < in->req_idx[d - 1])) return RL_E_INVALID;
+    run = (d && q == in->req_idx[d - 1]) ? run + 1 : 1;
+    if (run > 65535u) return RL_E_INVALID;
+    const uint32_t e0 = in->entry_first[d], e1 = in->entry_first[d + 1];
+    if (e1 < e0 || e1 > ne || e1 - e0 > 65535u || in->desc_off[d + 1] < in->desc_off[d]) return RL_E_INVALID;
+    uint64_t bytes = 0;
+    for (uint32_t e = e0; e < e1; e++) bytes += (uint64_t)in->key_len[e] + in->value_len[e] + 2u;
+    if (bytes != (uint64_t)(in->desc_off[d + 1] - in->desc_off[d])) return RL_E_INVALID;
+    if (in->override_flags && (in->override_flags[d] & 1u)) nov++;
+  }
+  const uint32_t dom_total = in->domain_off[nq], ent_total = in->desc_off[n];
+  if ((dom_total && !in->domain_bytes) || (ent_total && !in->desc_bytes)) return RL_E_INVALID;
+  const uint32_t tiles = (nq + RL_REQUESTS_TILE - 1) / RL_REQUESTS_TILE;
+  uint64_t need = 0;
+  auto section = [&need](uint64_t bytes) {
+    const uint64_t o = need;
+    need += (bytes + 3) & ~3ull;
+    return o;
+  };
+  rl_request_batch_packed p;
+  memset(&p, 0, sizeof p);
+  p.n_requests = nq;
+  p.n_descriptors = n;
+  p.n_entries = ne;
+  p.n_rules = in->n_rules;
+  p.n_overrides = nov;
+  p.index = section(16ull * (tiles + 1));
+  p.req = section(4ull * nq);
+  p.now = section(4ull * nq);
+  p.hits = section(4ull * nq);
+  p.desc = section(2ull * n);
+  p.key_len = section(2ull * ne);
+  p.value_len = section(2ull * ne);
+  p.overrides = section(sizeof(rl_request_override) * (uint64_t)nov);
+  p.domain_bytes = section(dom_total);
+  p.entry_bytes = section(ent_total);
+  if (!buf || buf_cap < need) {
+    out->buf_bytes = need;
+    return RL_E_CAPACITY;
+  }
+  p.buf = buf;
+  p.buf_bytes = need;
+  // (the sections' padding to 4 bytes is written too: the buffer is a function of the batch)
+  auto put = [buf](uint64_t off, const void* src, uint64_t bytes) {
+    if (bytes) memcpy(buf + off, src, bytes);
+    memset(buf + off + bytes, 0, ((bytes + 3) & ~3ull) - bytes);
+  };
+  uint32_t* index = reinterpret_cast<uint32_t*>(buf + p.index);
+  uint32_t* req = reinterpret_cast<uint32_t*>(buf + p.req);
+  uint32_t* now = reinterpret_cast<uint32_t*>(buf + p.now);
+  uint16_t* desc = reinterpret_cast<uint16_t*>(buf + p.desc);
+  rl_request_override* ov = reinterpret_cast<rl_request_override*>(buf + p.overrides);
+  uint32_t d = 0;
+  for (uint32_t q = 0; q < nq; q++) {
+    if (q % RL_REQUESTS_TILE == 0) {
+      uint32_t* ix = index + 4ull * (q / RL_REQUESTS_TILE);
+      ix[0] = d;
+      ix[1] = in->entry_first[d];
+      ix[2] = in->domain_off[q];
+      ix[3] = in->desc_off[d];
+    }
+    const uint32_t d0 = d;
+    while (d < n && in->req_idx[d] == q) d++;
+    req[q] = (d - d0) | (in->domain_off[q + 1] - in->domain_off[q]) << 16;
+    now[q] = (uint32_t)in->now[q];
+  }
+  uint32_t* tot = index + 4ull * tiles;
+  tot[0] = n;
+  tot[1] = ne;
+  tot[2] = dom_total;
+  tot[3] = ent_total;
+  put(p.hits, in->hits, 4ull * nq);
+  for (uint32_t i = 0, k = 0; i < n; i++) {
+    desc[i] = (uint16_t)(in->entry_first[i + 1] - in->entry_first[i]);
+    if (in->override_flags && (in->override_flags[i] & 1u)) {
+      rl_request_override& o = ov[k++];
+      o.descriptor = i;
+      o.requests_per_unit = in->override_rpu[i];
+      o.rule_id = in->override_rule[i];
+      o.unit = in->override_unit[i];
+      o.reserved[0] = o.reserved[1] = o.reserved[2] = 0;
+    }
+  }
+  if (n & 1u) desc[n] = 0;
+  put(p.key_len, in->key_len, 2ull * ne);
+  put(p.value_len, in->value_len, 2ull * ne);
+  put(p.domain_bytes, in->domain_bytes, dom_total);
+  put(p.entry_bytes, in->desc_bytes, ent_total);
+  *out = p;
+  return RL_OK;
+}
+
 }  // extern "C"

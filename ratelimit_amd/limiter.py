@@ -113,6 +113,15 @@ class PinnedArena:
         self.ptrs = []
 
 
+class PackedRequests(NamedTuple):
+    """A request batch in the one-buffer layout (Backend.pack_requests)."""
+    struct: object                  # abi.RlRequestBatchPacked (its buf points into ``buf``)
+    buf: np.ndarray                 # the buffer: pinned when packed into a PinnedArena
+    n_requests: int
+    n_descriptors: int
+    n_rules: int
+
+
 class Backend:
     """Owns one rl_ctx (one GPU's table)."""
 
@@ -293,6 +302,49 @@ class Backend:
         res.update({k: a[:nq] for k, a in ver.items()})
         res["global_shadow"] = int(gs[0])
         return res
+
+    def pack_requests(self, arrays: dict, n_rules: int, arena: Optional[PinnedArena] = None) -> PackedRequests:
+        """rl_request_batch_pack: pack_requests() arrays -> the one-buffer layout
+        of rl_do_limit_requests_packed_async, in a buffer from ``arena`` (pinned:
+        the copy is asynchronous) or, without one, in pageable memory."""
+        n, nq = len(arrays["req_idx"]), len(arrays["hits"])
+        b = abi.RlRequestBatch()
+        b.n_requests, b.n_descriptors, b.n_entries, b.n_rules = nq, n, len(arrays["key_len"]), n_rules
+        for k in abi.REQUEST_ARRAYS:
+            setattr(b, k, abi.ptr(arrays[k]))
+        p = abi.RlRequestBatchPacked()
+        rc = self.L.rl_request_batch_pack(C.byref(b), None, 0, C.byref(p))
+        if rc != abi.RL_E_CAPACITY:
+            raise RedisError("rl_request_batch_pack: malformed request batch [%s]" % abi.STATUS_NAMES.get(rc, rc), rc)
+        size = int(p.buf_bytes)
+        buf = arena.array(size, np.uint8) if arena is not None else np.zeros(max(size, 1), np.uint8)
+        rc = self.L.rl_request_batch_pack(C.byref(b), abi.ptr(buf), size, C.byref(p))
+        if rc:
+            raise RedisError("rl_request_batch_pack failed [%s]" % abi.STATUS_NAMES.get(rc, rc), rc)
+        return PackedRequests(p, buf, nq, n, n_rules)
+
+    def do_limit_requests_packed_async(self, packed: PackedRequests, out: Optional[dict], verdict: Optional[dict],
+                                       global_shadow: bool = False):
+        """rl_do_limit_requests_packed_async: nothing waited for. ``out``: numpy
+        arrays by rl_request_result field (any subset; None: no per-descriptor
+        bytes come back); ``verdict``: numpy arrays by rl_request_verdict field
+        (``global_shadow``: one uint64). Both are final after synchronize(), or
+        once batch_progress() counts the batch complete; they and ``packed``
+        must stay alive and untouched until then."""
+        r = v = None
+        if out is not None:
+            r = abi.RlRequestResult()
+            for k in out:
+                setattr(r, k, abi.ptr(out[k]))
+        if verdict is not None:
+            v = abi.RlRequestVerdict()
+            for k in verdict:
+                setattr(v, k, abi.ptr(verdict[k]))
+        opts = abi.RL_VERDICT_OPT_GLOBAL_SHADOW if global_shadow else 0
+        self._check(self.L.rl_do_limit_requests_packed_async(self.ctx, C.byref(packed.struct),
+                                                              C.byref(r) if r is not None else None, opts,
+                                                              C.byref(v) if v is not None else None))
+        return r, v
 
     def debug_verdict(self, n_requests, req_idx, match, code, limit_remaining, reset_s, requests_per_unit,
                       global_shadow: bool = False) -> dict:
@@ -722,6 +774,56 @@ class GpuRateLimitService:
         a = pack_requests(requests, nows, self.interner)
         n_rules = max(len(self.interner.keys), 1)
         res = self.backend.do_limit_requests_verdict(a, n_rules, self.global_shadow_mode, per_descriptor)
+        return self._verdicts(requests, res, per_descriptor)
+
+    def should_rate_limit_verdicts_pipelined(self, batches, per_descriptor: bool = True):
+        """``batches``: a list of (requests, nows). Every batch is submitted
+        through ``rl_do_limit_requests_packed_async`` without waiting, then one
+        synchronize(). -> what should_rate_limit_verdicts returns for each
+        batch, in order."""
+        from .config import pack_requests
+        for requests, _ in batches:  # checkServiceErr (ratelimit.go:151-152)
+            for r in requests:
+                if r.domain == "":
+                    raise ValueError("rate limit domain must not be empty")
+                if not r.descriptors:
+                    raise ValueError("rate limit descriptor list must not be empty")
+        arena = PinnedArena()
+        try:
+            flight = []
+            for requests, nows in batches:
+                a = pack_requests(requests, nows, self.interner)
+                n_rules = max(len(self.interner.keys), 1)
+                p = self.backend.pack_requests(a, n_rules, arena)
+                n, nq = p.n_descriptors, p.n_requests
+                out = {}
+                if per_descriptor:
+                    out = {k: arena.array(n, dt) for k, dt in abi.REQUEST_RESULT_DTYPES.items()}
+                out["stats"] = arena.array(n_rules * abi.RL_NUM_STATS, np.uint64)
+                ver = {k: arena.array(nq, dt) for k, dt in abi.REQUEST_VERDICT_DTYPES.items()}
+                ver["global_shadow"] = arena.array(1, np.uint64)
+                ver["global_shadow"][0] = 0
+                keep = self.backend.do_limit_requests_packed_async(p, out, ver, self.global_shadow_mode)
+                flight.append((requests, p, out, ver, keep))
+            self.backend.synchronize()
+            answers = []
+            for requests, p, out, ver, _ in flight:
+                res = {k: a[:p.n_descriptors] for k, a in out.items() if k != "stats"}
+                res["stats"] = out["stats"][:p.n_rules * abi.RL_NUM_STATS]
+                res.update({k: a[:p.n_requests] for k, a in ver.items() if k != "global_shadow"})
+                res["global_shadow"] = int(ver["global_shadow"][0])
+                answers.append(self._verdicts(requests, res, per_descriptor))
+            return answers
+        finally:
+            if self.backend.ctx:
+                try:
+                    self.backend.synchronize()  # (a failed flight: nothing may still write into the arena)
+                except RedisError:
+                    pass
+            arena.close()
+
+    def _verdicts(self, requests, res, per_descriptor):
+        """One batch's device answers -> should_rate_limit_verdicts' result."""
         self._add_stats(res["stats"])
         self.global_shadow_count += res["global_shadow"]
         out = []
