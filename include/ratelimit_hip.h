@@ -743,6 +743,70 @@ int rl_do_limit_requests_packed_async(rl_ctx* ctx, const rl_request_batch_packed
                                       rl_request_result* out, uint32_t opts,
                                       rl_request_verdict* verdict);
 
+/* ---- Serialized requests parsed on the GPU ---------------------------------
+ * The request path from the gRPC payloads themselves: the serialized
+ * envoy.service.ratelimit.v3.RateLimitRequest messages cross PCIe as they
+ * arrived, in one pinned buffer with one offset and one clock per request, and
+ * are parsed on the device into what rl_packer_pack and rl_request_batch_pack
+ * build on the host. The host reads the two ends of msg_off and no payload byte.
+ *
+ * Per-message status (wire->req_status), defined by the host packer:
+ *  - RL_WIRE_MALFORMED exactly where rl_packer_pack on that message alone
+ *    returns RL_E_INVALID;
+ *  - RL_WIRE_DEFERRED for a well-formed message that carries a descriptor with
+ *    `limit` (its stats key is a host-interned string) or exceeds the packed
+ *    layout's per-item limits (more than 65535 descriptors, a descriptor of
+ *    more than 65535 entries, a domain over 65535 bytes): the caller resubmits
+ *    it through the host packer;
+ *  - RL_WIRE_OK otherwise, parsed as the packer parses it.
+ * A deferred or malformed request takes part in the batch as a request
+ * without descriptors: no table effect, no stats, desc_first[q + 1] ==
+ * desc_first[q], the verdict entries of an empty request except
+ * overall_code[q] = 0 (no rl_code), never counted in global_shadow. For
+ * RL_WIRE_OK requests the answers, stats, statuses and table effects are
+ * those of rl_do_limit_requests_packed_async on the batch rl_packer_pack and
+ * rl_request_batch_pack make of the same messages with every other message
+ * replaced by an empty one.
+ *
+ * Errors at the call (nothing enqueued): RL_E_INVALID for a null in, wire or
+ * wire->req_status, out and verdict both null, a section outside buf or not
+ * 4-byte aligned, msg_off[0] != 0 or msg_off[n_requests] != msgs_bytes, a
+ * non-zero reserved field, unknown opts, no config loaded, a multi-shard ctx
+ * or one that joined a communicator; RL_E_CAPACITY for n_requests >
+ * max_requests or n_rules > max_rules. On the device: a decreasing msg_off
+ * fails the batch with RL_E_INVALID at rl_synchronize; a batch of more
+ * descriptors than min(desc_cap, max_batch) (desc_cap counts only with out
+ * non-NULL) or more entry bytes than max_stem_bytes fails with RL_E_CAPACITY
+ * there. A failed batch leaves the table untouched and later batches run
+ * normally. out, verdict, rl_batch_progress, rl_synchronize and the order
+ * against other entry points are those of rl_do_limit_requests_packed_async;
+ * wire's arrays are read when out's and verdict's are. */
+#define RL_WIRE_TILE 256u
+enum rl_wire_status { RL_WIRE_OK = 0, RL_WIRE_DEFERRED = 1, RL_WIRE_MALFORMED = 2 };
+
+typedef struct rl_wire_batch {
+  uint32_t n_requests;
+  uint32_t n_rules;      /* config rule ids are < n_rules (this path carries no override rules) */
+  const uint8_t* buf;    /* pinned host memory (rl_alloc_host): copied once, asynchronously */
+  uint64_t buf_bytes;
+  /* sections of buf, byte offsets, each a multiple of 4 */
+  uint64_t msg_off;      /* uint32[n_requests + 1]: message q = msgs[msg_off[q], msg_off[q+1]); msg_off[0] == 0 */
+  uint64_t now;          /* uint32[n_requests] UnixNow() (as rl_request_batch_packed.now) */
+  uint64_t msgs;         /* the serialized RateLimitRequest payloads, concatenated */
+  uint64_t msgs_bytes;   /* == msg_off[n_requests], < 2^32 */
+} rl_wire_batch;
+
+typedef struct rl_wire_result {   /* host memory */
+  uint8_t*  req_status;    /* [n_requests] rl_wire_status; required */
+  uint32_t* desc_first;    /* [n_requests + 1] first descriptor of each request in out's arrays; may be NULL */
+  uint32_t* n_descriptors; /* [1] descriptors of the batch; may be NULL */
+  uint32_t  desc_cap;      /* capacity, in descriptors, of out's per-descriptor arrays */
+  uint32_t  reserved;      /* zero */
+} rl_wire_result;
+
+int rl_do_limit_wire_async(rl_ctx* ctx, const rl_wire_batch* in, rl_wire_result* wire,
+                           rl_request_result* out, uint32_t opts, rl_request_verdict* verdict);
+
 /* Diagnostics (parity tests, like rl_debug_decide): the device verdict alone on
  * explicit per-descriptor answers in host arrays. req_idx must be non-decreasing
  * and < n_requests (RL_E_INVALID); n_descriptors <= max_batch and n_requests <=

@@ -22,7 +22,8 @@ EXPORTS = ["rl_abi_version", "rl_create", "rl_destroy", "rl_last_error", "rl_do_
            "rl_packer_last_error", "rl_comm_unique_id", "rl_comm_loopback_id", "rl_comm_init", "rl_do_limit_routed_async",
            "rl_do_limit_host_async", "rl_do_limit_compact_async", "rl_do_limit_prefixed_async", "rl_batch_progress",
            "rl_debug_log_tear", "rl_export_range", "rl_import", "rl_lookup", "rl_do_limit_requests_verdict",
-           "rl_debug_verdict", "rl_request_batch_pack", "rl_do_limit_requests_packed_async"]
+           "rl_debug_verdict", "rl_request_batch_pack", "rl_do_limit_requests_packed_async",
+           "rl_do_limit_wire_async"]
 
 _libs = {}
 
@@ -130,6 +131,10 @@ def load(path):
         L.rl_do_limit_requests_packed_async.argtypes = [C.c_void_p, C.POINTER(abi.RlRequestBatchPacked),
                                                         C.POINTER(abi.RlRequestResult), C.c_uint32,
                                                         C.POINTER(abi.RlRequestVerdict)]
+    if hasattr(L, "rl_do_limit_wire_async"):  # (A/B runs load the parent's library)
+        L.rl_do_limit_wire_async.argtypes = [C.c_void_p, C.POINTER(abi.RlWireBatch), C.POINTER(abi.RlWireResult),
+                                             C.POINTER(abi.RlRequestResult), C.c_uint32,
+                                             C.POINTER(abi.RlRequestVerdict)]
     if L.rl_abi_version() != abi.ABI_VERSION:
         raise RuntimeError("libratelimit_hip.so ABI mismatch")
     _libs[path] = L

@@ -148,6 +148,22 @@ class RlRequestBatchPacked(C.Structure):
                 ("index", C.c_uint64)]
 
 
+RL_WIRE_TILE = 256  # include/ratelimit_hip.h
+RL_WIRE_OK, RL_WIRE_DEFERRED, RL_WIRE_MALFORMED = 0, 1, 2  # enum rl_wire_status
+
+
+class RlWireBatch(C.Structure):
+    """rl_wire_batch: serialized RateLimitRequest payloads in one pinned buffer (sections as byte offsets)."""
+    _fields_ = [("n_requests", C.c_uint32), ("n_rules", C.c_uint32), ("buf", P), ("buf_bytes", C.c_uint64),
+                ("msg_off", C.c_uint64), ("now", C.c_uint64), ("msgs", C.c_uint64), ("msgs_bytes", C.c_uint64)]
+
+
+class RlWireResult(C.Structure):
+    """rl_wire_result: per-message status and each request's first descriptor (rl_do_limit_wire_async)."""
+    _fields_ = [("req_status", P), ("desc_first", P), ("n_descriptors", P), ("desc_cap", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 # the per-request arrays of rl_request_verdict (global_shadow apart: one uint64)
 REQUEST_VERDICT_DTYPES = {"overall_code": np.uint8, "flags": np.uint8, "min_descriptor": np.uint32,
                           "header_limit": np.uint32, "header_remaining": np.uint32, "header_reset_s": np.uint32}

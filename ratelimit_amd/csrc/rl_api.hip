@@ -937,6 +937,15 @@ int rl_do_limit_requests_packed_async(rl_ctx* c, const rl_request_batch_packed* 
   return eng_do_limit_requests_packed_async(c->e[0], in, out, opts, verdict);
 }
 
+int rl_do_limit_wire_async(rl_ctx* c, const rl_wire_batch* in, rl_wire_result* wire, rl_request_result* out,
+                           uint32_t opts, rl_request_verdict* verdict) {
+  if (!c) return fail(c, RL_E_INVALID, "gpu: null ctx");
+  const char* single = "gpu: rl_do_limit_wire_async is for single-shard ctxs";
+  if (c->n > 1) return fail(c, RL_E_INVALID, single);
+  if (c->comm) return eng_fail(c->e[0], RL_E_INVALID, single);
+  return eng_do_limit_wire_async(c->e[0], in, wire, out, opts, verdict);
+}
+
 int rl_debug_verdict(rl_ctx* c, uint32_t n_requests, uint32_t n_descriptors, const uint32_t* req_idx,
                      const uint8_t* match, const uint8_t* code, const uint32_t* limit_remaining,
                      const uint32_t* reset_s, const uint32_t* requests_per_unit, uint32_t opts,

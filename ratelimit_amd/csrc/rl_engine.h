@@ -69,6 +69,22 @@ struct RequestSlot {
   rl_request_result out{};
   rl_request_verdict verdict{};
   bool has_out = false, has_verdict = false;
+  // A wire batch (eng_do_limit_wire_async) has one more stage before the first
+  // half above: at the call only the buffer's copy, k_wire_count and the way
+  // of its count words to h_wcnt are enqueued (stage 1); once wire_done has
+  // fired, the middle stage (capacity checks, the carve by the now-known
+  // sizes, k_wire_emit, the config match and the matched count) follows on the
+  // same stream and the batch waits for its second half like a packed one
+  // (stage 0). The middle stage touches no table state, so it does not wait
+  // for the batch's turn. failed: refused by the middle stage's checks.
+  uint32_t stage = 0;
+  bool wire = false, failed = false;
+  uint8_t* wbuf = nullptr;       // the count stage's arrays (sized by the request count), allocated on first use
+  size_t wbuf_cap = 0;
+  uint32_t* h_wcnt = nullptr;    // pinned [8]: descriptors, entries, domain bytes, entry bytes, error bits
+  hipEvent_t wire_done = nullptr;
+  WireDev w{};
+  rl_wire_result wres{};
 };
 
 struct Engine {
@@ -257,7 +273,12 @@ int eng_requests_packed_check(Engine* c, const rl_request_batch_packed* in, cons
                               const rl_request_verdict* verdict, uint32_t* tiles);
 int eng_do_limit_requests_packed_async(Engine* c, const rl_request_batch_packed* in, rl_request_result* out,
                                        uint32_t opts, rl_request_verdict* verdict);
-// Enqueue the second halves of the oldest pending packed request batches, in
+// rl_do_limit_wire_async on this engine (rl_wire.hip parses the payloads).
+int eng_do_limit_wire_async(Engine* c, const rl_wire_batch* in, rl_wire_result* wire, rl_request_result* out,
+                            uint32_t opts, rl_request_verdict* verdict);
+// Enqueue the middle stage of every pending wire batch whose count words have
+// arrived (it touches no table state, so it need not wait for its turn), then
+// the second halves of the oldest pending request batches, wire or packed, in
 // submission order: the first `must` of them after waiting for their counts,
 // then every further one whose count has already arrived (hipEventQuery).
 // Every engine entry point but the packed one and eng_batch_progress passes

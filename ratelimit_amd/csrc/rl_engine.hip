@@ -1794,11 +1794,13 @@ void free_request_slots(Engine* c) {
     RequestSlot& s = c->rq[j];
     HostSlot& h = s.h;
     void* bufs[] = {h.stem, h.off, h.req, h.limit, h.hits, h.rule, h.now, h.unit, h.flags, h.code, h.rem,
-                    h.reset, h.stats, h.cbuf, s.mbuf};
+                    h.reset, h.stats, h.cbuf, s.mbuf, s.wbuf};
     for (void* p : bufs)
       if (p) (void)hipFree(p);
     if (s.h_cnt) (void)hipHostFree(s.h_cnt);
+    if (s.h_wcnt) (void)hipHostFree(s.h_wcnt);
     if (s.count_done) (void)hipEventDestroy(s.count_done);
+    if (s.wire_done) (void)hipEventDestroy(s.wire_done);
     if (h.in_done) (void)hipEventDestroy(h.in_done);
   }
   if (c->rq_copy) (void)hipStreamDestroy(c->rq_copy);
@@ -1858,13 +1860,20 @@ struct ToHostList {
 // The second half of the batch in slot s, whose count has arrived.
 int request_second_half(Engine* c, RequestSlot& s) {
   HostSlot& h = s.h;
-  const uint32_t n = s.n, nq = s.nq, bits = s.h_cnt[2];
   const uint64_t seq = s.seq;
+  if (s.failed) {  // a wire batch its middle stage refused (rq_fail is set): its place in the progress ring only
+    HIPCHK(c, hipEventRecord(c->done_ring[seq % PROGRESS_RING], s.st));
+    return RL_OK;
+  }
+  const uint32_t n = s.n, nq = s.nq, bits = s.h_cnt[2];
   if (bits) {
     // failed in the match stage: no second half, the table untouched; its
     // place in the progress ring completes with the work before it
     if (!c->rq_fail) {
-      if (bits & MATCH_ERR_UNPACK) {
+      if (bits & MATCH_ERR_WIRE) {
+        c->rq_fail = RL_E_INVALID;
+        c->rq_fail_msg = "gpu: wire batch: a message's second walk left its counted share";
+      } else if (bits & MATCH_ERR_UNPACK) {
         c->rq_fail = RL_E_INVALID;
         c->rq_fail_msg = "gpu: malformed packed request batch (tile index or override list)";
       } else if (bits & MATCH_ERR_REQ) {
@@ -1905,8 +1914,17 @@ int request_second_half(Engine* c, RequestSlot& s) {
     const VerdictDev vd = verdict_view(nq, n, s.opts, s.r.req, s.ro.match, s.ro.code, s.ro.rem, s.ro.reset, s.ro.rpu,
                                        s.vblock);
     HIPCHK(c, launch_verdict(vd, s.vblock, a));
+    if (s.wire) {  // a deferred or malformed request's entry is no answer
+      launch_wire_code(s.w.status, s.vblock + verdict_layout(nq).o_code, nq, a);
+      HIPCHK(c, hipGetLastError());
+    }
   }
   ToHostList th(a);
+  if (s.wire) {
+    th.add(s.wres.req_status, s.w.status, nq);
+    th.add(s.wres.desc_first, s.w.desc_first, (nq + 1) * 4ull);
+    th.add(s.wres.n_descriptors, s.w.cnt, 4);
+  }
   if (s.has_out) {
     const rl_request_result& out = s.out;
     th.add(out.code, s.ro.code, n);
@@ -1938,17 +1956,141 @@ int request_second_half(Engine* c, RequestSlot& s) {
   return RL_OK;
 }
 
+// The middle stage of the wire batch in slot s, whose count words have arrived:
+// the capacity checks, the carve by the now-known sizes, k_wire_emit, the
+// config match and the matched count's way to the host.
+int request_middle(Engine* c, RequestSlot& s) {
+  HostSlot& h = s.h;
+  hipStream_t st = s.st;
+  s.stage = 0;
+  const uint32_t n = s.h_wcnt[0], ne = s.h_wcnt[1], dom_total = s.h_wcnt[2], ent_total = s.h_wcnt[3];
+  const uint32_t bits = s.h_wcnt[4], nq = s.nq;
+  const rl_config& g = c->cfg;
+  int fail = 0;
+  const char* msg = nullptr;
+  if (bits & WIRE_ERR_OFF) {
+    fail = RL_E_INVALID;
+    msg = "gpu: wire batch msg_off decreasing or past msgs_bytes";
+  } else if ((bits & WIRE_ERR_SUM) || n > g.max_batch || (s.has_out && n > s.wres.desc_cap)) {
+    fail = RL_E_CAPACITY;
+    msg = "gpu: wire batch has more descriptors than desc_cap / max_batch";
+  } else if (ent_total > g.max_stem_bytes) {
+    fail = RL_E_CAPACITY;
+    msg = "gpu: request batch's entry bytes exceed max_stem_bytes";
+  }
+  if (fail) {
+    if (!c->rq_fail) {
+      c->rq_fail = fail;
+      c->rq_fail_msg = msg;
+    }
+    s.failed = true;
+    HIPCHK(c, hipEventRecord(s.count_done, st));
+    return RL_OK;
+  }
+  const size_t scan = n ? match_scan_bytes(n) : 0;
+  size_t need = 0;
+  auto piece = [&need](size_t bytes) {
+    const size_t o = need;
+    need += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
+    return o;
+  };
+  const size_t o_domoff = piece((nq + 1) * 4ull), o_req = piece(n * 4ull), o_ent = piece((n + 1) * 4ull),
+               o_doff = piece((n + 1) * 4ull), o_hits = piece(nq * 4ull), o_klen = piece(ne * 2ull),
+               o_vlen = piece(ne * 2ull), o_dom = piece(dom_total), o_desc = piece(ent_total), o_v = piece(n * 16ull),
+               o_kind = piece(n * 4ull), o_rpu = piece(n * 4ull), o_rule = piece(n * 4ull), o_cnt = piece(16),
+               o_code = piece(n), o_rem = piece(n * 4ull), o_reset = piece(n * 4ull), o_match = piece(n),
+               o_orule = piece(n * 4ull), o_orpu = piece(n * 4ull), o_ounit = piece(n), o_tmp = piece(scan);
+  const size_t o_verdict = s.has_verdict ? piece(verdict_layout(nq).bytes) : 0;
+  if (need > s.mbuf_cap) {  // (the count words are here: the slot's stream has nothing older in flight)
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (s.mbuf) HIPCHK(c, hipFree(s.mbuf));
+    s.mbuf = nullptr;
+    s.mbuf_cap = 0;
+    HIPCHK(c, hipMalloc((void**)&s.mbuf, need));
+    s.mbuf_cap = need;
+  }
+  uint8_t* M = s.mbuf;
+  HIPCHK(c, hipMemsetAsync(M + o_cnt, 0, 16, st));
+  MatchBuf m{(unsigned long long*)(M + o_v), (uint32_t*)(M + o_kind), (uint32_t*)(M + o_rpu),
+             (uint32_t*)(M + o_rule), (uint32_t*)(M + o_cnt)};
+  WireOut wo;
+  wo.tot = make_uint4(n, ne, dom_total, ent_total);
+  wo.dom_off = (uint32_t*)(M + o_domoff);
+  wo.hits = (uint32_t*)(M + o_hits);
+  wo.now = h.now;
+  wo.req = (uint32_t*)(M + o_req);
+  wo.ent_first = (uint32_t*)(M + o_ent);
+  wo.desc_off = (uint32_t*)(M + o_doff);
+  wo.klen = (uint16_t*)(M + o_klen);
+  wo.vlen = (uint16_t*)(M + o_vlen);
+  wo.dom = M + o_dom;
+  wo.desc = M + o_desc;
+  wo.err = m.count + 2;
+  if (!nq) HIPCHK(c, hipMemsetAsync(wo.dom_off, 0, 4, st));
+  launch_wire_emit(s.w, wo, st);
+  ReqDev r;
+  r.n_req = nq;
+  r.n_desc = n;
+  r.n_ent = ne;
+  r.dom_total = dom_total;
+  r.desc_total = ent_total;
+  r.dom = wo.dom;
+  r.dom_off = wo.dom_off;
+  r.hits = wo.hits;
+  r.req = wo.req;
+  r.ent_first = wo.ent_first;
+  r.desc_off = wo.desc_off;
+  r.desc = wo.desc;
+  r.klen = wo.klen;
+  r.vlen = wo.vlen;
+  r.ovf = nullptr;
+  r.ov_rpu = nullptr;
+  r.ov_unit = nullptr;
+  r.ov_rule = nullptr;
+  PackOut po{h.stem, h.off, h.req, h.unit, h.flags, h.limit, h.hits, h.rule, g.max_stem_bytes};
+  launch_match(c->cfg_dev, r, m, po, M + o_tmp, scan, st);
+  HIPCHK(c, hipGetLastError());
+  ToHost th{};
+  th.src[0] = M + o_cnt;
+  th.dst[0] = (uint8_t*)s.h_cnt;
+  th.bytes[0] = 16;
+  th.n = 1;
+  HIPCHK(c, copy_to_host(th, st));
+  HIPCHK(c, hipEventRecord(s.count_done, st));
+  s.n = n;
+  s.r = r;
+  s.m = m;
+  s.ro = ReqOutDev{M + o_code, (uint32_t*)(M + o_rem), (uint32_t*)(M + o_reset), M + o_match,
+                   (uint32_t*)(M + o_orule), (uint32_t*)(M + o_orpu), M + o_ounit};
+  s.vblock = s.has_verdict ? M + o_verdict : nullptr;
+  return RL_OK;
+}
+
 }  // namespace
 
 int eng_requests_advance(Engine* c, uint32_t must) {
   if (!c->rq_n) return RL_OK;
   HIPCHK(c, hipSetDevice(c->cfg.device));
+  // wire batches whose count words have arrived: their middle stages, oldest first
+  for (uint32_t i = 0; i < c->rq_n; i++) {
+    RequestSlot& s = c->rq[(c->rq_head + i) % RL_REQUESTS_INFLIGHT];
+    if (s.stage != 1) continue;
+    const hipError_t e = hipEventQuery(s.wire_done);
+    if (e == hipErrorNotReady) break;
+    HIPCHK(c, e);
+    if (const int rc = request_middle(c, s)) return rc;
+  }
   while (c->rq_n) {
     RequestSlot& s = c->rq[c->rq_head];
     if (must) {
+      if (s.stage == 1) {
+        HIPCHK(c, hipEventSynchronize(s.wire_done));
+        if (const int rc = request_middle(c, s)) return rc;
+      }
       HIPCHK(c, hipEventSynchronize(s.count_done));
       must--;
     } else {
+      if (s.stage == 1) break;
       const hipError_t e = hipEventQuery(s.count_done);
       if (e == hipErrorNotReady) break;
       HIPCHK(c, e);
@@ -2071,6 +2213,118 @@ int eng_do_limit_requests_packed_async(Engine* c, const rl_request_batch_packed*
   s.ro = ReqOutDev{M + o_code, (uint32_t*)(M + o_rem), (uint32_t*)(M + o_reset), M + o_match,
                    (uint32_t*)(M + o_orule), (uint32_t*)(M + o_orpu), M + o_ounit};
   s.vblock = verdict ? M + o_verdict : nullptr;
+  s.has_out = out != nullptr;
+  s.has_verdict = verdict != nullptr;
+  s.stage = 0;
+  s.wire = s.failed = false;
+  if (out) s.out = *out;
+  if (verdict) s.verdict = *verdict;
+  if (verdict && !nq && verdict->global_shadow) *verdict->global_shadow = 0;
+  c->rq_n++;
+  return RL_OK;
+}
+
+// ---- serialized payloads parsed on the device (rl_do_limit_wire_async) ------
+
+int eng_do_limit_wire_async(Engine* c, const rl_wire_batch* in, rl_wire_result* wire, rl_request_result* out,
+                            uint32_t opts, rl_request_verdict* verdict) {
+  if (!c || !in || !wire || !wire->req_status || (!out && !verdict))
+    return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
+  if (wire->reserved) return set_err(c, RL_E_INVALID, "gpu: rl_wire_result: reserved field not zero");
+  if (!c->cfg_loaded) return set_err(c, RL_E_INVALID, "gpu: no rate limit configuration loaded");
+  const rl_config& g = c->cfg;
+  const uint32_t nq = in->n_requests;
+  if (nq > g.max_requests || in->n_rules > g.max_rules)
+    return set_err(c, RL_E_CAPACITY, "gpu: wire batch exceeds configured max_requests/max_rules");
+  const uint64_t B = in->buf_bytes;
+  if (!in->buf) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  auto sect = [&](uint64_t off, uint64_t bytes) { return off % 4 == 0 && off <= B && bytes <= B - off; };
+  if (in->msgs_bytes > 0xFFFFFFFFull || !sect(in->msg_off, (nq + 1) * 4ull) || !sect(in->now, nq * 4ull) ||
+      !sect(in->msgs, in->msgs_bytes))
+    return set_err(c, RL_E_INVALID, "gpu: wire batch section outside buf or not 4-byte aligned");
+  // (the two ends only: every offset between them is checked on the device)
+  const uint32_t* mo = reinterpret_cast<const uint32_t*>(in->buf + in->msg_off);
+  if (mo[0] || mo[nq] != in->msgs_bytes)
+    return set_err(c, RL_E_INVALID, "gpu: wire batch msg_off does not start at zero or end at msgs_bytes");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  int rc;
+  if ((rc = ensure_request_slots(c))) return rc;
+  if ((rc = eng_requests_advance(c, c->rq_n == RL_REQUESTS_INFLIGHT ? 1 : 0))) return rc;
+  RequestSlot& s = c->rq[(c->rq_head + c->rq_n) % RL_REQUESTS_INFLIGHT];
+  HostSlot& h = s.h;
+  hipStream_t st = s.st;  // (after the slot's previous batch, in stream order)
+  if (!s.h_wcnt) {
+    HIPCHK(c, hipHostMalloc((void**)&s.h_wcnt, 32, hipHostMallocDefault));
+    HIPCHK(c, hipEventCreateWithFlags(&s.wire_done, hipEventDisableTiming));
+  }
+  const uint32_t T = (nq + RL_WIRE_TILE - 1) / RL_WIRE_TILE;
+  size_t need = 0;
+  auto piece = [&need](size_t bytes) {
+    const size_t o = need;
+    need += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
+    return o;
+  };
+  const size_t o_reqw = piece(nq * 16ull), o_tsum = piece(T * 16ull), o_index = piece((T + 1) * 16ull),
+               o_cnt = piece(32), o_status = piece(nq), o_first = piece((nq + 1) * 4ull);
+  if (need > s.wbuf_cap || B > h.cbuf_cap) HIPCHK(c, hipStreamSynchronize(st));  // the slot's previous batch
+  if (need > s.wbuf_cap) {
+    if (s.wbuf) HIPCHK(c, hipFree(s.wbuf));
+    s.wbuf = nullptr;
+    s.wbuf_cap = 0;
+    HIPCHK(c, hipMalloc((void**)&s.wbuf, need));
+    s.wbuf_cap = need;
+  }
+  if (B > h.cbuf_cap) {
+    if (h.cbuf) HIPCHK(c, hipFree(h.cbuf));
+    h.cbuf = nullptr;
+    h.cbuf_cap = 0;
+    HIPCHK(c, dalloc(&h.cbuf, B + 64));
+    h.cbuf_cap = B;
+  }
+  if (c->seq_sub - c->seq_done >= PROGRESS_RING) {
+    HIPCHK(c, hipEventSynchronize(c->done_ring[c->seq_done % PROGRESS_RING]));
+    c->seq_done++;
+  }
+  if (B) {  // (on the copy stream, as the packed batches' buffers)
+    HIPCHK(c, hipMemcpyAsync(h.cbuf, in->buf, B, hipMemcpyHostToDevice, c->rq_copy));
+    HIPCHK(c, hipEventRecord(h.in_done, c->rq_copy));
+    HIPCHK(c, hipStreamWaitEvent(st, h.in_done, 0));
+  }
+  uint8_t* W = s.wbuf;
+  WireDev w;
+  w.n_req = nq;
+  w.tiles = T;
+  w.msgs_bytes = (uint32_t)in->msgs_bytes;
+  w.msg_off = (const uint32_t*)(h.cbuf + in->msg_off);
+  w.now32 = (const uint32_t*)(h.cbuf + in->now);
+  w.msgs = h.cbuf + in->msgs;
+  w.reqw = (uint4*)(W + o_reqw);
+  w.tsum = (uint4*)(W + o_tsum);
+  w.index = (uint4*)(W + o_index);
+  w.cnt = (uint32_t*)(W + o_cnt);
+  w.status = W + o_status;
+  w.desc_first = (uint32_t*)(W + o_first);
+  HIPCHK(c, hipMemsetAsync(w.cnt, 0, 32, st));
+  launch_wire_count(w, st);
+  HIPCHK(c, hipGetLastError());
+  ToHost th{};
+  th.src[0] = (const uint8_t*)w.cnt;
+  th.dst[0] = (uint8_t*)s.h_wcnt;
+  th.bytes[0] = 32;
+  th.n = 1;
+  HIPCHK(c, copy_to_host(th, st));
+  HIPCHK(c, hipEventRecord(s.wire_done, st));
+  s.stage = 1;
+  s.wire = true;
+  s.failed = false;
+  s.w = w;
+  s.wres = *wire;
+  s.n = 0;
+  s.nq = nq;
+  s.n_rules = in->n_rules;
+  s.opts = opts;
+  s.seq = c->seq_sub++;
   s.has_out = out != nullptr;
   s.has_verdict = verdict != nullptr;
   if (out) s.out = *out;

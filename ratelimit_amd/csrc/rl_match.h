@@ -170,6 +170,49 @@ void launch_unpack_requests(const rl_request_batch_packed& pb, const uint8_t* bu
 // (verdict_layout(v.n_req), whose pointers v holds), then k_verdict and
 // k_verdict_final.
 hipError_t launch_verdict(const VerdictDev& v, uint8_t* block, hipStream_t st);
+// ---- serialized RateLimitRequest payloads parsed on the device (rl_wire.hip)
+constexpr uint32_t MATCH_ERR_WIRE = 8;  // k_wire_emit: a message's re-walk left its counted share
+// error bits of the count stage (WireDev::cnt[4])
+constexpr uint32_t WIRE_ERR_OFF = 1;    // msg_off decreasing or past msgs_bytes
+constexpr uint32_t WIRE_ERR_SUM = 2;    // a batch total does not fit 32 bits
+
+// A wire batch on the device: the sections of the copied buffer and the
+// count stage's arrays (sized by the request count alone).
+struct WireDev {
+  uint32_t n_req, tiles, msgs_bytes;
+  const uint32_t* msg_off;  // [n_req + 1]
+  const uint32_t* now32;    // [n_req]
+  const uint8_t* msgs;
+  uint4* reqw;     // [n_req] {descriptors | status << 24, entries, domain bytes, entry bytes}; zero counts unless OK
+  uint4* tsum;     // [tiles] the tiles' sums of those four
+  uint4* index;    // [tiles + 1] their exclusive scan: rl_request_batch_packed's tile index
+  uint32_t* cnt;   // [8] the totals {descriptors, entries, domain bytes, entry bytes}, error bits
+  uint8_t* status;        // [n_req] rl_wire_status
+  uint32_t* desc_first;   // [n_req + 1]
+};
+
+// What k_wire_emit writes: ReqDev's arrays (all but the overrides) and the clocks.
+struct WireOut {
+  uint4 tot;  // the count stage's totals, capacity-checked on the host
+  uint32_t* dom_off;
+  uint32_t* hits;
+  int64_t* now;
+  uint32_t* req;
+  uint32_t* ent_first;
+  uint32_t* desc_off;
+  uint16_t* klen;
+  uint16_t* vlen;
+  uint8_t* dom;
+  uint8_t* desc;
+  uint32_t* err;  // MatchBuf::count + 2
+};
+
+// k_wire_count per tile, then the scan over the tiles (index, totals, desc_first[n_req]).
+void launch_wire_count(const WireDev& w, hipStream_t st);
+void launch_wire_emit(const WireDev& w, const WireOut& o, hipStream_t st);
+// overall_code[q] = 0 where status[q] != RL_WIRE_OK
+void launch_wire_code(const uint8_t* status, uint8_t* o_code, uint32_t n_req, hipStream_t st);
+
 VerdictDev verdict_view(uint32_t n_req, uint32_t n_desc, uint32_t opts, const uint32_t* req, const uint8_t* match,
                         const uint8_t* code, const uint32_t* rem, const uint32_t* reset, const uint32_t* rpu,
                         uint8_t* block);

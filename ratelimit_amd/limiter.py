@@ -122,6 +122,14 @@ class PackedRequests(NamedTuple):
     n_rules: int
 
 
+class WireRequests(NamedTuple):
+    """Serialized RateLimitRequest payloads in the one-buffer layout of rl_wire_batch (Backend.wire_batch)."""
+    struct: object                  # abi.RlWireBatch (its buf points into ``buf``)
+    buf: np.ndarray                 # the buffer: pinned when built in a PinnedArena
+    n_requests: int
+    msgs_bytes: int
+
+
 class Backend:
     """Owns one rl_ctx (one GPU's table)."""
 
@@ -345,6 +353,66 @@ class Backend:
                                                               C.byref(r) if r is not None else None, opts,
                                                               C.byref(v) if v is not None else None))
         return r, v
+
+    @staticmethod
+    def wire_batch(msgs, nows, arena: Optional[PinnedArena] = None, n_rules: int = 1) -> WireRequests:
+        """Serialized RateLimitRequest payloads (``msgs``: bytes objects) and one
+        UnixNow() per request -> the one-buffer layout of rl_do_limit_wire_async:
+        [msg_off u32 x (n + 1) | now u32 x n | payload bytes], each section 4-byte
+        aligned, in a buffer from ``arena`` (pinned: the copy is asynchronous) or,
+        without one, in pageable memory. The payloads are only copied: numpy
+        alone, no parsing."""
+        nq = len(msgs)
+        lens = np.fromiter((len(m) for m in msgs), np.uint64, nq)
+        total = int(lens.sum())
+        if total >= 1 << 32:
+            raise RedisError("wire batch: payload bytes do not fit 32 bits", abi.RL_E_CAPACITY)
+        o_off, o_now = 0, 4 * (nq + 1)
+        o_msgs = o_now + 4 * nq
+        size = (o_msgs + total + 3) & ~3
+        buf = arena.array(size, np.uint8) if arena is not None else np.zeros(max(size, 1), np.uint8)
+        off = buf[o_off:o_now].view(np.uint32)
+        off[0] = 0
+        np.cumsum(lens, out=off[1:], dtype=np.uint32)
+        buf[o_now:o_msgs].view(np.uint32)[:] = np.asarray(nows, np.int64).astype(np.uint32)
+        buf[o_msgs:o_msgs + total] = np.frombuffer(b"".join(msgs), np.uint8)
+        buf[o_msgs + total:size] = 0
+        w = abi.RlWireBatch()
+        w.n_requests, w.n_rules = nq, n_rules
+        w.buf, w.buf_bytes = abi.ptr(buf), size
+        w.msg_off, w.now, w.msgs, w.msgs_bytes = o_off, o_now, o_msgs, total
+        return WireRequests(w, buf, nq, total)
+
+    def do_limit_wire_async(self, wb: WireRequests, wire: dict, out: Optional[dict], verdict: Optional[dict],
+                            global_shadow: bool = False, desc_cap: Optional[int] = None):
+        """rl_do_limit_wire_async: nothing waited for. ``wire``: numpy arrays
+        ``req_status`` (uint8 per request; required), ``desc_first`` (uint32 x
+        (n + 1)) and ``n_descriptors`` (one uint32), the latter two optional;
+        ``out`` and ``verdict`` as for do_limit_requests_packed_async, ``out``'s
+        per-descriptor arrays holding ``desc_cap`` descriptors (default: the
+        length of the shortest). All are final after synchronize(), or once
+        batch_progress() counts the batch complete; they and ``wb`` must stay
+        alive and untouched until then."""
+        wr = abi.RlWireResult()
+        for k in ("req_status", "desc_first", "n_descriptors"):
+            setattr(wr, k, abi.ptr(wire.get(k)))
+        r = v = None
+        if out is not None:
+            r = abi.RlRequestResult()
+            for k in out:
+                setattr(r, k, abi.ptr(out[k]))
+            if desc_cap is None:
+                desc_cap = min([len(a) for k, a in out.items() if k != "stats"] or [0])
+        wr.desc_cap = int(desc_cap or 0)
+        if verdict is not None:
+            v = abi.RlRequestVerdict()
+            for k in verdict:
+                setattr(v, k, abi.ptr(verdict[k]))
+        opts = abi.RL_VERDICT_OPT_GLOBAL_SHADOW if global_shadow else 0
+        self._check(self.L.rl_do_limit_wire_async(self.ctx, C.byref(wb.struct), C.byref(wr),
+                                                   C.byref(r) if r is not None else None, opts,
+                                                   C.byref(v) if v is not None else None))
+        return wr, r, v
 
     def debug_verdict(self, n_requests, req_idx, match, code, limit_remaining, reset_s, requests_per_unit,
                       global_shadow: bool = False) -> dict:
@@ -751,10 +819,11 @@ class GpuRateLimitService:
     def close(self):
         self.backend.close()
 
-    def _add_stats(self, deltas):
+    def _add_stats(self, deltas, keys=None):
+        keys = self.interner.keys if keys is None else keys
         st = deltas.reshape(-1, abi.RL_NUM_STATS)
         for i in np.nonzero(st.any(axis=1))[0]:
-            row = self.stats.setdefault(self.interner.keys[i], [0] * abi.RL_NUM_STATS)
+            row = self.stats.setdefault(keys[i], [0] * abi.RL_NUM_STATS)
             for j in range(abi.RL_NUM_STATS):
                 row[j] += int(st[i, j])
 
@@ -822,9 +891,88 @@ class GpuRateLimitService:
                     pass
             arena.close()
 
-    def _verdicts(self, requests, res, per_descriptor):
-        """One batch's device answers -> should_rate_limit_verdicts' result."""
-        self._add_stats(res["stats"])
+    def should_rate_limit_payloads_pipelined(self, batches, per_descriptor: bool = True):
+        """``batches``: a list of (payloads, nows), the payloads serialized
+        RateLimitRequest messages as the gRPC server received them. Every batch
+        goes through ``rl_do_limit_wire_async`` unparsed, without waiting, then
+        one synchronize(). The messages the device deferred (a descriptor with
+        a ``limit`` override, or past the packed layout's per-item limits) are
+        then resubmitted through ``RequestPacker`` and the packed path, batch by
+        batch: they take effect after every batch of this call, in batch order.
+        -> per batch what should_rate_limit_verdicts returns, a malformed
+        message's entry being a RedisError (that request's alone). As on the
+        wire nothing is checked before the device, an empty domain or
+        descriptor list is answered like any other request."""
+        from .config import RequestPacker, batch_arrays
+        arena = PinnedArena()
+        packer = None
+        try:
+            n_rules = max(len(self.interner.keys), 1)
+            max_batch = int(self.backend.cfg.max_batch)
+            flight = []
+            for msgs, nows in batches:
+                wb = self.backend.wire_batch(msgs, nows, arena, n_rules)
+                nq = len(msgs)
+                cap = max(min(max_batch, wb.msgs_bytes // 2), 1)  # (a descriptor takes 2 payload bytes at least)
+                out = {}
+                if per_descriptor:
+                    out = {k: arena.array(cap, dt) for k, dt in abi.REQUEST_RESULT_DTYPES.items()}
+                out["stats"] = arena.array(n_rules * abi.RL_NUM_STATS, np.uint64)
+                ver = {k: arena.array(nq, dt) for k, dt in abi.REQUEST_VERDICT_DTYPES.items()}
+                ver["global_shadow"] = arena.array(1, np.uint64)
+                ver["global_shadow"][0] = 0
+                wire = {"req_status": arena.array(nq, np.uint8), "desc_first": arena.array(nq + 1, np.uint32),
+                        "n_descriptors": arena.array(1, np.uint32)}
+                keep = self.backend.do_limit_wire_async(wb, wire, out, ver, self.global_shadow_mode, cap)
+                flight.append((wb, wire, out, ver, keep))
+            self.backend.synchronize()
+            answers = []
+            again = []  # (batch, its deferred messages' indices)
+            for b, (wb, wire, out, ver, _) in enumerate(flight):
+                nq, n = wb.n_requests, int(wire["n_descriptors"][0])
+                res = {k: a[:n] for k, a in out.items() if k != "stats"}
+                res["stats"] = out["stats"][:n_rules * abi.RL_NUM_STATS]
+                res.update({k: a[:nq] for k, a in ver.items() if k != "global_shadow"})
+                res["global_shadow"] = int(ver["global_shadow"][0])
+                first = wire["desc_first"][:nq + 1]
+                vs, shadow = self._verdicts(first[1:] - first[:-1], res, per_descriptor)
+                status = wire["req_status"][:nq]
+                for q in np.nonzero(status == abi.RL_WIRE_MALFORMED)[0]:
+                    vs[q] = RedisError("gpu: malformed RateLimitRequest", abi.RL_E_INVALID)
+                deferred = np.nonzero(status == abi.RL_WIRE_DEFERRED)[0]
+                if len(deferred):
+                    again.append((b, deferred))
+                answers.append([vs, shadow])
+            for b, deferred in again:
+                msgs, nows = batches[b]
+                if packer is None:
+                    packer = RequestPacker(len(self.interner.keys))
+                rb = packer.pack([msgs[q] for q in deferred], [nows[q] for q in deferred])
+                a = batch_arrays(rb)
+                nr = max(packer.rules(), 1)
+                res = self.backend.do_limit_requests_verdict(a, nr, self.global_shadow_mode, per_descriptor)
+                keys = self.interner.keys + [packer.rule_key(i) for i in range(len(self.interner.keys), nr)]
+                counts = np.bincount(a["req_idx"], minlength=len(deferred))
+                vs, shadow = self._verdicts(counts, res, per_descriptor, keys)
+                for q, v in zip(deferred, vs):
+                    answers[b][0][q] = v
+                answers[b][1] += shadow
+            return [tuple(x) for x in answers]
+        finally:
+            if packer is not None:
+                packer.close()
+            if self.backend.ctx:
+                try:
+                    self.backend.synchronize()  # (a failed flight: nothing may still write into the arena)
+                except RedisError:
+                    pass
+            arena.close()
+
+    def _verdicts(self, requests, res, per_descriptor, keys=None):
+        """One batch's device answers -> should_rate_limit_verdicts' result.
+        ``requests``: the requests, or their descriptor counts; ``keys``: the
+        stats keys by rule id (default: the config's)."""
+        self._add_stats(res["stats"], keys)
         self.global_shadow_count += res["global_shadow"]
         out = []
         d = 0
@@ -832,7 +980,7 @@ class GpuRateLimitService:
             sts = None
             if per_descriptor:
                 sts = []
-                for _ in r.descriptors:
+                for _ in range(len(r.descriptors) if hasattr(r, "descriptors") else int(r)):
                     if int(res["match"][d]) == abi.RL_MATCH_LIMIT:
                         sts.append(DescriptorStatus(int(res["code"][d]),
                                                     Limit(int(res["requests_per_unit"][d]), int(res["unit"][d])),

@@ -263,3 +263,32 @@ def c1_requests(tenants, now, hits=None):
         "value_len": np.tile(np.array([11, 3], np.uint16), n),
         "override_flags": None, "override_rpu": None, "override_unit": None, "override_rule": None,
     }
+
+
+def c1_payloads(tenants, hits=None):
+    """c1_requests as the gRPC payloads: one serialized
+    envoy.service.ratelimit.v3.RateLimitRequest per request (domain ``bench``,
+    the two descriptors, hits_addend), every message 85 bytes -> uint8[nq, 85].
+    rl_packer_pack on them gives c1_requests' arrays."""
+    tenants = np.asarray(tenants, np.int64)
+
+    def fb(f, data):  # a length-delimited field (lengths below 128)
+        return bytes([f << 3 | 2, len(data)]) + data
+
+    def entry(k, v):
+        return fb(1, fb(1, k) + fb(2, v))
+
+    t0 = b"t" + b"0" * 10
+    msg = fb(1, b"bench") + b"".join(fb(2, entry(b"tenant", t0) + entry(b"tier", tier)) for tier in (b"sec", b"min"))
+    msg += bytes([3 << 3, 1])
+    rows = np.tile(np.frombuffer(msg, np.uint8), (tenants.size, 1))
+    digits = _digits(tenants, 10)
+    p = msg.find(t0)
+    while p >= 0:
+        rows[:, p + 1:p + 11] = digits
+        p = msg.find(t0, p + 1)
+    if hits is not None:
+        h = np.asarray(hits, np.uint32)
+        assert h.min() >= 1 and h.max() < 128  # (one varint byte; proto3 omits a zero)
+        rows[:, -1] = h
+    return rows

@@ -20,8 +20,20 @@ back with one rl_synchronize at the end, under the same --verdict modes. A
 buffer and its outputs are reused only once rl_batch_progress counts their
 previous batch complete (a ring of PACKED_RING buffers), as a batcher would.
 
+--path wire-async submits the same batches as serialized RateLimitRequest
+payloads (rl_do_limit_wire_async: parsed on the GPU), from a ring of
+PACKED_RING pinned buffers in the same way.
+
+--from-payloads starts both pipelined paths from the same C1 payload bytes in
+pageable memory, inside the timed loop: packed-async runs rl_packer_pack +
+rl_request_batch_pack on each batch's messages, split over --pack-threads N
+(<= 16) host threads, each slice submitted as its own packed batch; wire-async
+copies the payload bytes into its pinned buffer and writes the offsets and
+clocks.
+
     python scripts/bench_requests.py [--config c1|c2] [--steps K] [--verdict off|full|only]
-                                     [--path sync|packed-async]
+                                     [--path sync|packed-async|wire-async]
+                                     [--from-payloads [--pack-threads N]]
 """
 import argparse
 import ctypes as C
@@ -58,8 +70,14 @@ def main():
     ap.add_argument("--requests", type=int, default=500_000)
     ap.add_argument("--tenants", type=int, default=10_000_000)
     ap.add_argument("--verdict", default="off", choices=["off", "full", "only"])
-    ap.add_argument("--path", default="sync", choices=["sync", "packed-async"])
+    ap.add_argument("--path", default="sync", choices=["sync", "packed-async", "wire-async"])
+    ap.add_argument("--from-payloads", action="store_true")
+    ap.add_argument("--pack-threads", type=int, default=1)
     args = ap.parse_args()
+    if args.from_payloads and args.path == "sync":
+        ap.error("--from-payloads goes with --path packed-async or wire-async")
+    if not 1 <= args.pack_threads <= 16:
+        ap.error("--pack-threads: 1..16")
     nq, T = args.requests, args.tenants
     rng = np.random.default_rng(0xC1 if args.config == "c1" else 0xC2)
     zs = W.ZipfSampler(T, 1.1) if args.config == "c2" else None
@@ -68,10 +86,12 @@ def main():
     be_pk = Backend(0.8, False, **kw)
     tree = ConfigTree.from_yaml([("c1.yaml", W.C1_CONFIG_YAML)])
     be_req.load_config(tree)
-    batches = []
+    batches, payloads = [], []
     for b in range(4):
         t = zs.sample(rng, nq) if zs is not None else rng.integers(0, T, nq)
         h = rng.integers(1, 9, nq) if args.config == "c2" else None
+        if args.path == "wire-async" or args.from_payloads:
+            payloads.append(W.c1_payloads(t, h))  # (pageable: the bytes as the gRPC server received them)
         raw = {k: pinned(v) for k, v in W.c1_requests(t, W.NOW0 + b, h).items()}
         pk, n, _, nr = W.c1_batch(t, W.NOW0 + b, h)
         batches.append((raw, {k: pinned(v) for k, v in pk.items()}, n))
@@ -117,7 +137,7 @@ def main():
     packed_bytes = None
     if hasattr(lib(), "rl_request_batch_pack"):
         packed_bytes = int(be_req.pack_requests(batches[0][0], 2).struct.buf_bytes)
-    if args.path == "packed-async":
+    if args.path == "packed-async" and not args.from_payloads:
         for j in range(PACKED_RING):
             p = be_req.pack_requests(batches[j % 4][0], 2, arena)
             out = None
@@ -131,9 +151,92 @@ def main():
             ring.append((p, out, ver, p.buf[p.struct.now:p.struct.now + 4 * nq].view(np.uint32)))
 
     def async_call(j, now):
+        if args.path == "wire-async":
+            return wire_call(j, now)
         p, out, ver, now32 = ring[j]
         now32[:] = now
         return be_req.do_limit_requests_packed_async(p, out, ver)
+
+    # --path wire-async: PACKED_RING pinned wire buffers (offsets | clocks | payload bytes) and output sets
+    wire_bytes = None
+    if args.path == "wire-async":
+        for j in range(PACKED_RING):
+            wb = be_req.wire_batch([r.tobytes() for r in payloads[j % 4]], [W.NOW0] * nq, arena, 2)
+            wire_bytes = int(wb.struct.buf_bytes)
+            out = None
+            if args.verdict != "only":
+                out = {k: arena.array(n, dt) for k, dt in abi.REQUEST_RESULT_DTYPES.items()}
+                out["stats"] = arena.array(2 * abi.RL_NUM_STATS, np.uint64)
+            ver = None
+            if args.verdict != "off":
+                ver = {k: arena.array(nq, dt) for k, dt in abi.REQUEST_VERDICT_DTYPES.items()}
+                ver["global_shadow"] = arena.array(1, np.uint64)
+            wire = {"req_status": arena.array(nq, np.uint8), "n_descriptors": arena.array(1, np.uint32)}
+            ws = wb.struct
+            ring.append((wb, out, ver, wb.buf[ws.now:ws.now + 4 * nq].view(np.uint32), wire,
+                         wb.buf[ws.msg_off:ws.msg_off + 4 * (nq + 1)].view(np.uint32),
+                         wb.buf[ws.msgs:ws.msgs + ws.msgs_bytes]))
+    L_msg = payloads[0].shape[1] if payloads else 0
+    msg_off32 = (np.arange(nq + 1, dtype=np.uint64) * L_msg).astype(np.uint32)
+
+    def wire_call(j, now, b=None):
+        wb, out, ver, now32, wire, off32, body = ring[j]
+        if b is not None:  # --from-payloads: the host's work per batch
+            body[:] = payloads[b].reshape(-1)
+            off32[:] = msg_off32
+        now32[:] = now
+        return be_req.do_limit_wire_async(wb, wire, out, ver, False, n)
+
+    # --from-payloads on packed-async: each batch's messages split over the pack threads, every slice
+    # parsed (rl_packer_pack) and laid out (rl_request_batch_pack) by its thread, then submitted
+    NT = args.pack_threads
+    pack_ring, pool = [], None
+    if args.from_payloads and args.path == "packed-async":
+        from concurrent.futures import ThreadPoolExecutor
+        pool = ThreadPoolExecutor(NT)
+        cut = [nq * k // NT for k in range(NT + 1)]
+        L = lib()
+        for j in range(PACKED_RING):
+            slots = []
+            for k in range(NT):
+                m = cut[k + 1] - cut[k]
+                probe = be_req.pack_requests(W.c1_requests(np.zeros(m, np.int64), W.NOW0), 2)  # (its size)
+                size = int(probe.struct.buf_bytes)
+                out = None
+                if args.verdict != "only":
+                    out = {key: arena.array(2 * m, dt) for key, dt in abi.REQUEST_RESULT_DTYPES.items()}
+                    out["stats"] = arena.array(2 * abi.RL_NUM_STATS, np.uint64)
+                ver = None
+                if args.verdict != "off":
+                    ver = {key: arena.array(m, dt) for key, dt in abi.REQUEST_VERDICT_DTYPES.items()}
+                    ver["global_shadow"] = arena.array(1, np.uint64)
+                slots.append(dict(buf=arena.array(size, np.uint8), size=size, out=out, ver=ver,
+                                  packer=L.rl_packer_create(2), rb=abi.RlRequestBatch(),
+                                  p=abi.RlRequestBatchPacked(), nows=np.zeros(m, np.int64),
+                                  off=(np.arange(m + 1, dtype=np.uint64) * L_msg), m=m))
+            pack_ring.append(slots)
+
+        def pack_slice(sl, body, now):
+            sl["nows"][:] = now
+            rc = L.rl_packer_pack(sl["packer"], abi.ptr(body), abi.ptr(sl["off"]), sl["m"], abi.ptr(sl["nows"]),
+                                  C.byref(sl["rb"]))
+            assert rc == 0
+            sl["rb"].n_rules = 2
+            rc = L.rl_request_batch_pack(C.byref(sl["rb"]), abi.ptr(sl["buf"]), sl["size"], C.byref(sl["p"]))
+            assert rc == 0, rc
+            return sl
+
+    def packed_from_payloads(j, b, now):
+        from ratelimit_amd.limiter import PackedRequests
+        flat = payloads[b].reshape(-1)
+        futs = [pool.submit(pack_slice, sl, flat[cut[k] * L_msg:cut[k + 1] * L_msg], now)
+                for k, sl in enumerate(pack_ring[j])]
+        keep = []
+        for f in futs:  # (submitted in slice order, as each is ready)
+            sl = f.result()
+            keep.append(be_req.do_limit_requests_packed_async(
+                PackedRequests(sl["p"], sl["buf"], sl["m"], 2 * sl["m"], 2), sl["out"], sl["ver"]))
+        return keep
 
     # warm-up + equality of the two paths on the same stream (clock +1 s per step)
     for s in range(8 if args.path == "sync" else 0):
@@ -152,13 +255,31 @@ def main():
             want = np.ones(nq, np.uint8)
             np.maximum.at(want, raw["req_idx"], pr["code"])
             assert np.array_equal(vr["overall_code"], want), "overall_code"
-    for s in range(8 if args.path == "packed-async" else 0):
+    sub_batches = NT if pack_ring else 1  # packed batches submitted per step
+    for s in range(8 if args.path != "sync" else 0):
         pk = batches[s % 4][1]
         pk["now"][:] = W.NOW0 + s
-        async_call(s % PACKED_RING, W.NOW0 + s)
+        if pack_ring:
+            packed_from_payloads(s % PACKED_RING, s % 4, W.NOW0 + s)
+        elif args.from_payloads:
+            wire_call(s % PACKED_RING, W.NOW0 + s, s % 4)
+        else:
+            async_call(s % PACKED_RING, W.NOW0 + s)
         be_req.synchronize()
         pk_call(pk)
-        _, out, ver, _ = ring[s % PACKED_RING]
+        if pack_ring:  # the slices' outputs side by side are the batch's
+            sl = pack_ring[s % PACKED_RING]
+            out = ver = None
+            if sl[0]["out"] is not None:
+                out = {k: np.concatenate([x["out"][k][:2 * x["m"]] for x in sl]) for k in abi.REQUEST_RESULT_DTYPES}
+                out["stats"] = np.sum([x["out"]["stats"] for x in sl], axis=0)
+            if sl[0]["ver"] is not None:
+                ver = {"overall_code": np.concatenate([x["ver"]["overall_code"][:x["m"]] for x in sl])}
+        else:
+            out, ver = ring[s % PACKED_RING][1:3]
+        if args.path == "wire-async":
+            wire = ring[s % PACKED_RING][4]
+            assert not wire["req_status"].any() and int(wire["n_descriptors"][0]) == n
         if out is not None:
             for k in ("code", "limit_remaining", "reset_s"):
                 assert np.array_equal(out[k], pr[k]), k
@@ -169,14 +290,20 @@ def main():
             np.maximum.at(want, batches[s % 4][0]["req_idx"], pr["code"])
             assert np.array_equal(ver["overall_code"], want), "overall_code"
     res = {}
-    if args.path == "packed-async":
+    if args.path != "sync":
         base = be_req.batch_progress()[0]
         keep = []
         t0 = time.perf_counter()
         for s in range(args.steps):
-            while be_req.batch_progress()[1] - base + PACKED_RING <= s:  # the buffer's previous batch is complete
+            # the buffer's previous batch is complete
+            while be_req.batch_progress()[1] - base + PACKED_RING * sub_batches <= s * sub_batches:
                 pass
-            keep.append(async_call(s % PACKED_RING, W.NOW0 + 8 + s))
+            if pack_ring:
+                keep.append(packed_from_payloads(s % PACKED_RING, s % 4, W.NOW0 + 8 + s))
+            elif args.from_payloads:
+                keep.append(wire_call(s % PACKED_RING, W.NOW0 + 8 + s, s % 4))
+            else:
+                keep.append(async_call(s % PACKED_RING, W.NOW0 + 8 + s))
         be_req.synchronize()
         res["requests"] = time.perf_counter() - t0
         t0 = time.perf_counter()
@@ -195,6 +322,8 @@ def main():
     path = "rl_do_limit_requests" if args.verdict == "off" else "rl_do_limit_requests_verdict"
     if args.path == "packed-async":
         path = "rl_do_limit_requests_packed_async"
+    if args.path == "wire-async":
+        path = "rl_do_limit_wire_async"
     out = {"path": path + " (host buffers, PCIe-inclusive)", "config": args.config.upper(),
            "verdict": args.verdict, "d2h_bytes_per_descriptor": d2h / n,
            "descriptors_per_batch": n, "steps": args.steps,
@@ -207,9 +336,12 @@ def main():
            "parity": "request path == packed DoLimit path on 8 warm-up batches"}
     if packed_bytes is not None:  # the one-buffer layout of the same batch (rl_request_batch_pack)
         out["packed_request_bytes_per_descriptor"] = packed_bytes / n
-    if args.path == "packed-async":
+    if args.path != "sync":
         out["path"] = path + " (one pinned buffer per batch, pipelined, PCIe-inclusive)"
-        out["h2d_bytes_per_descriptor"] = packed_bytes / n
+        out["h2d_bytes_per_descriptor"] = (wire_bytes if args.path == "wire-async" else packed_bytes) / n
+        out["from_payloads"] = bool(args.from_payloads)
+        if pack_ring:
+            out["pack_threads"] = NT
     print(json.dumps(out))
 
 
