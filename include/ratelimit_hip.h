@@ -807,6 +807,89 @@ typedef struct rl_wire_result {   /* host memory */
 int rl_do_limit_wire_async(rl_ctx* ctx, const rl_wire_batch* in, rl_wire_result* wire,
                            rl_request_result* out, uint32_t opts, rl_request_verdict* verdict);
 
+/* ---- Serialized responses written on the GPU --------------------------------
+ * The way back of the wire path: one serialized
+ * envoy.service.ratelimit.v3.RateLimitResponse per request, as gRPC marshals
+ * what shouldRateLimitWorker builds (ratelimit.go:161-210), written on the
+ * device from the per-descriptor answers and the verdict. The bytes are the
+ * canonical proto3 encoding (fields in field-number order, zero scalars and
+ * empty strings omitted, minimal varints, a present sub-message written even
+ * when empty). For a request q with RL_WIRE_OK:
+ *   08 c                                  overall_code[q]
+ *   per descriptor, in order:  12 L body  body = 08 code
+ *                                           [12 M [08 requests_per_unit] 10 unit]   match == RL_MATCH_LIMIT
+ *                                           [18 limit_remaining]                    non-zero
+ *                                           [22 N [08 reset_s]]                     match == RL_MATCH_LIMIT
+ *   with header keys and min_descriptor[q] != RL_NO_DESCRIPTOR, three
+ *   HeaderValues (limit, remaining, reset):  1a H [0a klen key] 12 vlen digits
+ *   the digits being the decimal ASCII of header_limit / _remaining / _reset_s.
+ * A status has at most RL_RESPONSE_STATUS_MAX bytes (durations are below 2^21
+ * seconds: the longest window is a day). A deferred or malformed request gets
+ * an empty response (the host answers it itself); an RL_WIRE_OK request
+ * without descriptors answers 08 01. */
+#define RL_RESPONSE_KEY_MAX 64u
+#define RL_RESPONSE_STATUS_MAX 26u
+
+typedef struct rl_response_format {   /* read and copied at the call */
+  const uint8_t* limit_key;      /* the three header names; all NULL (or a NULL format): no headers */
+  const uint8_t* remaining_key;
+  const uint8_t* reset_key;
+  uint16_t limit_key_len;        /* each <= RL_RESPONSE_KEY_MAX; a NULL key's length is zero */
+  uint16_t remaining_key_len;
+  uint16_t reset_key_len;
+  uint16_t reserved;             /* zero */
+} rl_response_format;
+
+typedef struct rl_response_batch {    /* host memory */
+  uint8_t*  bytes;       /* pinned (rl_alloc_host): response q = bytes[resp_off[q], resp_off[q+1]) */
+  uint64_t  bytes_cap;   /* >= rl_response_bound(n_requests, the batch's descriptors, fmt) */
+  uint32_t* resp_off;    /* [n_requests + 1]; resp_off[0] == 0 */
+} rl_response_batch;
+
+/* No batch of n_requests requests over n_descriptors descriptors serializes to
+ * more: n_requests x (2 + 3 x 16 + the key lengths) + 26 x n_descriptors with
+ * headers, 2 x n_requests + 26 x n_descriptors without. Host code. */
+uint64_t rl_response_bound(uint32_t n_requests, uint32_t n_descriptors, const rl_response_format* fmt);
+
+/* rl_do_limit_wire_async plus the responses. out and verdict may both be NULL
+ * here (the device computes the verdict either way); wire is required as
+ * there. Only the used bytes of resp->bytes and resp_off cross PCIe; both are
+ * read when out's and verdict's arrays are. Errors at the call (nothing
+ * enqueued): those of rl_do_limit_wire_async, and RL_E_INVALID for a null
+ * resp, resp->bytes or resp->resp_off, bytes not page-locked over bytes_cap,
+ * a key over RL_RESPONSE_KEY_MAX bytes, a NULL key with a length, or a
+ * non-zero reserved field. The response length depends on the counters, so
+ * the capacity is checked by the bound once the descriptor count is known: a
+ * batch whose rl_response_bound exceeds bytes_cap or does not fit 32 bits
+ * fails with RL_E_CAPACITY at rl_synchronize, the table untouched, and later
+ * batches run normally. Single-shard ctxs only. */
+int rl_do_limit_wire_respond_async(rl_ctx* ctx, const rl_wire_batch* in, rl_wire_result* wire,
+                                   rl_request_result* out, uint32_t opts, rl_request_verdict* verdict,
+                                   const rl_response_format* fmt, rl_response_batch* resp);
+
+/* The host twin: the same bytes and offsets from answers in host arrays
+ * (request q's descriptors are [desc_first[q], desc_first[q+1]) of res's
+ * arrays). It serves the deferred requests that go through the host packer,
+ * and callers of the array paths. req_status may be NULL (every request
+ * RL_WIRE_OK). res needs code, limit_remaining, reset_s, match,
+ * requests_per_unit and unit; verdict needs overall_code and, with header
+ * keys, min_descriptor and the three header arrays (RL_E_INVALID). bytes ==
+ * NULL or bytes_cap too small: RL_E_CAPACITY, *bytes_needed = the exact bytes
+ * needed, resp_off filled, no byte written. Host code; no GPU needed. */
+int rl_response_serialize(uint32_t n_requests, const uint32_t* desc_first, const uint8_t* req_status,
+                          const rl_request_result* res, const rl_request_verdict* verdict,
+                          const rl_response_format* fmt, uint8_t* bytes, uint64_t bytes_cap,
+                          uint32_t* resp_off, uint64_t* bytes_needed);
+
+/* Diagnostics, like rl_debug_verdict: the device verdict and the device
+ * serializer on explicit per-descriptor answers in host arrays (answers: code,
+ * limit_remaining, reset_s, match, requests_per_unit, unit; reset_s < 2^21).
+ * req_status may be NULL. Synchronous; resp->bytes may be pageable here.
+ * RL_E_CAPACITY if rl_response_bound exceeds resp->bytes_cap. */
+int rl_debug_respond(rl_ctx* ctx, uint32_t n_requests, uint32_t n_descriptors, const uint32_t* req_idx,
+                     const uint8_t* req_status, const rl_request_result* answers, uint32_t opts,
+                     const rl_response_format* fmt, rl_response_batch* resp);
+
 /* Diagnostics (parity tests, like rl_debug_decide): the device verdict alone on
  * explicit per-descriptor answers in host arrays. req_idx must be non-decreasing
  * and < n_requests (RL_E_INVALID); n_descriptors <= max_batch and n_requests <=

@@ -23,7 +23,8 @@ EXPORTS = ["rl_abi_version", "rl_create", "rl_destroy", "rl_last_error", "rl_do_
            "rl_do_limit_host_async", "rl_do_limit_compact_async", "rl_do_limit_prefixed_async", "rl_batch_progress",
            "rl_debug_log_tear", "rl_export_range", "rl_import", "rl_lookup", "rl_do_limit_requests_verdict",
            "rl_debug_verdict", "rl_request_batch_pack", "rl_do_limit_requests_packed_async",
-           "rl_do_limit_wire_async"]
+           "rl_do_limit_wire_async", "rl_response_bound", "rl_do_limit_wire_respond_async", "rl_response_serialize",
+           "rl_debug_respond"]
 
 _libs = {}
 
@@ -135,6 +136,19 @@ def load(path):
         L.rl_do_limit_wire_async.argtypes = [C.c_void_p, C.POINTER(abi.RlWireBatch), C.POINTER(abi.RlWireResult),
                                              C.POINTER(abi.RlRequestResult), C.c_uint32,
                                              C.POINTER(abi.RlRequestVerdict)]
+    if hasattr(L, "rl_do_limit_wire_respond_async"):  # (A/B runs load the parent's library)
+        L.rl_response_bound.restype = C.c_uint64
+        L.rl_response_bound.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(abi.RlResponseFormat)]
+        L.rl_do_limit_wire_respond_async.argtypes = [C.c_void_p, C.POINTER(abi.RlWireBatch),
+                                                     C.POINTER(abi.RlWireResult), C.POINTER(abi.RlRequestResult),
+                                                     C.c_uint32, C.POINTER(abi.RlRequestVerdict),
+                                                     C.POINTER(abi.RlResponseFormat), C.POINTER(abi.RlResponseBatch)]
+        L.rl_response_serialize.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(abi.RlRequestResult),
+                                            C.POINTER(abi.RlRequestVerdict), C.POINTER(abi.RlResponseFormat),
+                                            C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.rl_debug_respond.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                       C.POINTER(abi.RlRequestResult), C.c_uint32, C.POINTER(abi.RlResponseFormat),
+                                       C.POINTER(abi.RlResponseBatch)]
     if L.rl_abi_version() != abi.ABI_VERSION:
         raise RuntimeError("libratelimit_hip.so ABI mismatch")
     _libs[path] = L

@@ -164,6 +164,35 @@ class RlWireResult(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+RL_RESPONSE_KEY_MAX = 64  # include/ratelimit_hip.h
+RL_RESPONSE_STATUS_MAX = 26
+
+
+class RlResponseFormat(C.Structure):
+    """rl_response_format: the three RateLimit-* header names of the serialized responses (all NULL: no headers)."""
+    _fields_ = [("limit_key", P), ("remaining_key", P), ("reset_key", P), ("limit_key_len", C.c_uint16),
+                ("remaining_key_len", C.c_uint16), ("reset_key_len", C.c_uint16), ("reserved", C.c_uint16)]
+
+
+class RlResponseBatch(C.Structure):
+    """rl_response_batch: the serialized RateLimitResponse payloads and their offsets (host memory)."""
+    _fields_ = [("bytes", P), ("bytes_cap", C.c_uint64), ("resp_off", P)]
+
+
+def make_response_format(header_keys):
+    """(limit, remaining, reset) header names as bytes, or None for no headers ->
+    (RlResponseFormat, the buffers it points into)."""
+    f = RlResponseFormat()
+    keep = []
+    if header_keys is not None:
+        for name, k in zip(("limit_key", "remaining_key", "reset_key"), header_keys):
+            b = C.create_string_buffer(bytes(k), max(len(k), 1))
+            keep.append(b)
+            setattr(f, name, C.cast(b, P))
+            setattr(f, name + "_len", len(k))
+    return f, keep
+
+
 # the per-request arrays of rl_request_verdict (global_shadow apart: one uint64)
 REQUEST_VERDICT_DTYPES = {"overall_code": np.uint8, "flags": np.uint8, "min_descriptor": np.uint32,
                           "header_limit": np.uint32, "header_remaining": np.uint32, "header_reset_s": np.uint32}

@@ -946,6 +946,25 @@ int rl_do_limit_wire_async(rl_ctx* c, const rl_wire_batch* in, rl_wire_result* w
   return eng_do_limit_wire_async(c->e[0], in, wire, out, opts, verdict);
 }
 
+int rl_do_limit_wire_respond_async(rl_ctx* c, const rl_wire_batch* in, rl_wire_result* wire, rl_request_result* out,
+                                   uint32_t opts, rl_request_verdict* verdict, const rl_response_format* fmt,
+                                   rl_response_batch* resp) {
+  if (!c) return fail(c, RL_E_INVALID, "gpu: null ctx");
+  const char* single = "gpu: rl_do_limit_wire_respond_async is for single-shard ctxs";
+  if (c->n > 1) return fail(c, RL_E_INVALID, single);
+  if (c->comm) return eng_fail(c->e[0], RL_E_INVALID, single);
+  if (!resp) return eng_fail(c->e[0], RL_E_INVALID, "gpu: null rl_response_batch");
+  return eng_do_limit_wire_async(c->e[0], in, wire, out, opts, verdict, fmt, resp);
+}
+
+int rl_debug_respond(rl_ctx* c, uint32_t n_requests, uint32_t n_descriptors, const uint32_t* req_idx,
+                     const uint8_t* req_status, const rl_request_result* answers, uint32_t opts,
+                     const rl_response_format* fmt, rl_response_batch* resp) {
+  if (!c) return fail(c, RL_E_INVALID, "gpu: null ctx");
+  return from_engine(c, c->e[0], eng_debug_respond(c->e[0], n_requests, n_descriptors, req_idx, req_status, answers,
+                                                    opts, fmt, resp));
+}
+
 int rl_debug_verdict(rl_ctx* c, uint32_t n_requests, uint32_t n_descriptors, const uint32_t* req_idx,
                      const uint8_t* match, const uint8_t* code, const uint32_t* limit_remaining,
                      const uint32_t* reset_s, const uint32_t* requests_per_unit, uint32_t opts,

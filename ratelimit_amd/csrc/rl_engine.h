@@ -85,6 +85,14 @@ struct RequestSlot {
   hipEvent_t wire_done = nullptr;
   WireDev w{};
   rl_wire_result wres{};
+  // rl_do_limit_wire_respond_async: the responses are serialized after the
+  // verdict (rl_resp.hip), in staging carved from mbuf by the middle stage
+  bool has_resp = false;
+  rlresp::Format fmt{};
+  rl_response_batch resp{};
+  uint8_t* resp_dst = nullptr;   // resp.bytes as the device sees it
+  size_t o_resp = 0;             // the staging's place in mbuf (resp_layout)
+  uint64_t resp_bound = 0;
 };
 
 struct Engine {
@@ -274,8 +282,10 @@ int eng_requests_packed_check(Engine* c, const rl_request_batch_packed* in, cons
 int eng_do_limit_requests_packed_async(Engine* c, const rl_request_batch_packed* in, rl_request_result* out,
                                        uint32_t opts, rl_request_verdict* verdict);
 // rl_do_limit_wire_async on this engine (rl_wire.hip parses the payloads).
+// fmt / resp: rl_do_limit_wire_respond_async (resp == nullptr: rl_do_limit_wire_async).
 int eng_do_limit_wire_async(Engine* c, const rl_wire_batch* in, rl_wire_result* wire, rl_request_result* out,
-                            uint32_t opts, rl_request_verdict* verdict);
+                            uint32_t opts, rl_request_verdict* verdict, const rl_response_format* fmt = nullptr,
+                            rl_response_batch* resp = nullptr);
 // Enqueue the middle stage of every pending wire batch whose count words have
 // arrived (it touches no table state, so it need not wait for its turn), then
 // the second halves of the oldest pending request batches, wire or packed, in
@@ -288,6 +298,9 @@ int eng_debug_verdict(Engine* c, uint32_t n_requests, uint32_t n_descriptors, co
                       const uint8_t* match, const uint8_t* code, const uint32_t* limit_remaining,
                       const uint32_t* reset_s, const uint32_t* requests_per_unit, uint32_t opts,
                       rl_request_verdict* verdict);
+int eng_debug_respond(Engine* c, uint32_t n_requests, uint32_t n_descriptors, const uint32_t* req_idx,
+                      const uint8_t* req_status, const rl_request_result* answers, uint32_t opts,
+                      const rl_response_format* fmt, rl_response_batch* resp);
 int eng_local_cache_info_get(Engine* c, int64_t now, rl_local_cache_info* info);
 int eng_snapshot_size(Engine* c, uint64_t* bytes);
 int eng_snapshot_save(Engine* c, void* host, uint64_t bytes);

@@ -1857,6 +1857,37 @@ struct ToHostList {
   }
 };
 
+// The serializer's view of one batch: its answers, its verdict block and its staging (resp_layout at `stage`).
+RespDev resp_view(uint32_t nq, uint32_t n, uint64_t bound, const uint32_t* req, const uint32_t* desc_first,
+                  const uint8_t* status, const ReqOutDev& ro, uint8_t* vblock, uint8_t* stage) {
+  const VerdictLayout V = verdict_layout(nq);
+  const RespLayout L = resp_layout(nq, n, bound);
+  RespDev r;
+  r.n_req = nq;
+  r.n_desc = n;
+  r.cap = (uint32_t)L.cap;
+  r.req = req;
+  r.desc_first = desc_first;
+  r.status = status;
+  r.code = ro.code;
+  r.rem = ro.rem;
+  r.reset = ro.reset;
+  r.match = ro.match;
+  r.rpu = ro.rpu;
+  r.unit = ro.unit;
+  r.o_code = vblock + V.o_code;
+  r.o_min = (const uint32_t*)(vblock + V.o_min);
+  r.o_limit = (const uint32_t*)(vblock + V.o_limit);
+  r.o_rem = (const uint32_t*)(vblock + V.o_rem);
+  r.o_reset = (const uint32_t*)(vblock + V.o_reset);
+  r.soff = (uint32_t*)(stage + L.soff);
+  r.resp_off = (uint32_t*)(stage + L.resp_off);
+  r.tmp = stage + L.tmp;
+  r.tmp_bytes = L.tmp_bytes;
+  r.bytes = stage + L.bytes;
+  return r;
+}
+
 // The second half of the batch in slot s, whose count has arrived.
 int request_second_half(Engine* c, RequestSlot& s) {
   HostSlot& h = s.h;
@@ -1910,7 +1941,7 @@ int request_second_half(Engine* c, RequestSlot& s) {
   s.st = a;
   launch_match_expand(s.r, s.m, h.code, h.rem, h.reset, s.ro, a);
   HIPCHK(c, hipGetLastError());
-  if (s.has_verdict && nq) {
+  if ((s.has_verdict || s.has_resp) && nq) {
     const VerdictDev vd = verdict_view(nq, n, s.opts, s.r.req, s.ro.match, s.ro.code, s.ro.rem, s.ro.reset, s.ro.rpu,
                                        s.vblock);
     HIPCHK(c, launch_verdict(vd, s.vblock, a));
@@ -1920,6 +1951,14 @@ int request_second_half(Engine* c, RequestSlot& s) {
     }
   }
   ToHostList th(a);
+  if (s.has_resp && nq) {  // the responses: serialized from the answers and the verdict where they lie
+    const RespDev rd = resp_view(nq, n, s.resp_bound, s.r.req, s.w.desc_first, s.w.status, s.ro, s.vblock,
+                                 s.mbuf + s.o_resp);
+    HIPCHK(c, launch_respond(rd, s.fmt, a));
+    launch_respond_to_host(rd, s.resp_dst, a);
+    HIPCHK(c, hipGetLastError());
+    th.add(s.resp.resp_off, rd.resp_off, (nq + 1) * 4ull);
+  }
   if (s.wire) {
     th.add(s.wres.req_status, s.w.status, nq);
     th.add(s.wres.desc_first, s.w.desc_first, (nq + 1) * 4ull);
@@ -1978,6 +2017,12 @@ int request_middle(Engine* c, RequestSlot& s) {
     fail = RL_E_CAPACITY;
     msg = "gpu: request batch's entry bytes exceed max_stem_bytes";
   }
+  // (the responses' length depends on the counters: the bound stands for it)
+  s.resp_bound = s.has_resp ? rlresp::bound(nq, n, s.fmt) : 0;
+  if (!fail && s.has_resp && (s.resp_bound > s.resp.bytes_cap || s.resp_bound >= (1ull << 32))) {
+    fail = RL_E_CAPACITY;
+    msg = "gpu: wire batch's rl_response_bound exceeds bytes_cap or 32 bits";
+  }
   if (fail) {
     if (!c->rq_fail) {
       c->rq_fail = fail;
@@ -2000,7 +2045,9 @@ int request_middle(Engine* c, RequestSlot& s) {
                o_kind = piece(n * 4ull), o_rpu = piece(n * 4ull), o_rule = piece(n * 4ull), o_cnt = piece(16),
                o_code = piece(n), o_rem = piece(n * 4ull), o_reset = piece(n * 4ull), o_match = piece(n),
                o_orule = piece(n * 4ull), o_orpu = piece(n * 4ull), o_ounit = piece(n), o_tmp = piece(scan);
-  const size_t o_verdict = s.has_verdict ? piece(verdict_layout(nq).bytes) : 0;
+  const bool has_v = s.has_verdict || s.has_resp;
+  const size_t o_verdict = has_v ? piece(verdict_layout(nq).bytes) : 0;
+  s.o_resp = s.has_resp && nq ? piece(resp_layout(nq, n, s.resp_bound).total) : 0;
   if (need > s.mbuf_cap) {  // (the count words are here: the slot's stream has nothing older in flight)
     HIPCHK(c, hipStreamSynchronize(st));
     if (s.mbuf) HIPCHK(c, hipFree(s.mbuf));
@@ -2062,7 +2109,7 @@ int request_middle(Engine* c, RequestSlot& s) {
   s.m = m;
   s.ro = ReqOutDev{M + o_code, (uint32_t*)(M + o_rem), (uint32_t*)(M + o_reset), M + o_match,
                    (uint32_t*)(M + o_orule), (uint32_t*)(M + o_orpu), M + o_ounit};
-  s.vblock = s.has_verdict ? M + o_verdict : nullptr;
+  s.vblock = has_v ? M + o_verdict : nullptr;
   return RL_OK;
 }
 
@@ -2216,7 +2263,7 @@ int eng_do_limit_requests_packed_async(Engine* c, const rl_request_batch_packed*
   s.has_out = out != nullptr;
   s.has_verdict = verdict != nullptr;
   s.stage = 0;
-  s.wire = s.failed = false;
+  s.wire = s.failed = s.has_resp = false;
   if (out) s.out = *out;
   if (verdict) s.verdict = *verdict;
   if (verdict && !nq && verdict->global_shadow) *verdict->global_shadow = 0;
@@ -2227,9 +2274,17 @@ int eng_do_limit_requests_packed_async(Engine* c, const rl_request_batch_packed*
 // ---- serialized payloads parsed on the device (rl_do_limit_wire_async) ------
 
 int eng_do_limit_wire_async(Engine* c, const rl_wire_batch* in, rl_wire_result* wire, rl_request_result* out,
-                            uint32_t opts, rl_request_verdict* verdict) {
-  if (!c || !in || !wire || !wire->req_status || (!out && !verdict))
+                            uint32_t opts, rl_request_verdict* verdict, const rl_response_format* fmt,
+                            rl_response_batch* resp) {
+  if (!c || !in || !wire || !wire->req_status || (!out && !verdict && !resp))
     return set_err(c, RL_E_INVALID, "gpu: null argument");
+  rlresp::Format rf{};
+  uint8_t* resp_dst = nullptr;
+  if (resp) {
+    if (!resp->bytes || !resp->resp_off) return set_err(c, RL_E_INVALID, "gpu: rl_response_batch without bytes or resp_off");
+    if (!rlresp::format_from(fmt, &rf))
+      return set_err(c, RL_E_INVALID, "gpu: rl_response_format: key over 64 bytes, NULL key with a length or reserved not zero");
+  }
   if (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
   if (wire->reserved) return set_err(c, RL_E_INVALID, "gpu: rl_wire_result: reserved field not zero");
   if (!c->cfg_loaded) return set_err(c, RL_E_INVALID, "gpu: no rate limit configuration loaded");
@@ -2248,6 +2303,18 @@ int eng_do_limit_wire_async(Engine* c, const rl_wire_batch* in, rl_wire_result* 
   if (mo[0] || mo[nq] != in->msgs_bytes)
     return set_err(c, RL_E_INVALID, "gpu: wire batch msg_off does not start at zero or end at msgs_bytes");
   HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (resp && resp->bytes_cap) {
+    // the responses go out by a kernel's stores: both ends inside one page-locked allocation
+    void* dp = nullptr;
+    void* de = nullptr;
+    if (hipHostGetDevicePointer(&dp, resp->bytes, 0) != hipSuccess || !dp ||
+        hipHostGetDevicePointer(&de, resp->bytes + resp->bytes_cap - 1, 0) != hipSuccess ||
+        (uint8_t*)de != (uint8_t*)dp + resp->bytes_cap - 1) {
+      (void)hipGetLastError();  // (the failed lookup's sticky error: pageable memory)
+      return set_err(c, RL_E_INVALID, "gpu: rl_response_batch.bytes is not page-locked over bytes_cap (rl_alloc_host)");
+    }
+    resp_dst = (uint8_t*)dp;
+  }
   int rc;
   if ((rc = ensure_request_slots(c))) return rc;
   if ((rc = eng_requests_advance(c, c->rq_n == RL_REQUESTS_INFLIGHT ? 1 : 0))) return rc;
@@ -2330,7 +2397,100 @@ int eng_do_limit_wire_async(Engine* c, const rl_wire_batch* in, rl_wire_result* 
   if (out) s.out = *out;
   if (verdict) s.verdict = *verdict;
   if (verdict && !nq && verdict->global_shadow) *verdict->global_shadow = 0;
+  s.has_resp = resp != nullptr;
+  if (resp) {
+    s.fmt = rf;
+    s.resp = *resp;
+    s.resp_dst = resp_dst;
+    if (!nq) resp->resp_off[0] = 0;
+  }
   c->rq_n++;
+  return RL_OK;
+}
+
+int eng_debug_respond(Engine* c, uint32_t nq, uint32_t n, const uint32_t* req_idx, const uint8_t* req_status,
+                      const rl_request_result* ans, uint32_t opts, const rl_response_format* fmt,
+                      rl_response_batch* resp) {
+  if (!c || !resp || !resp->resp_off || !ans) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  RQ_SETTLE(c);
+  if (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
+  rlresp::Format rf{};
+  if (!rlresp::format_from(fmt, &rf))
+    return set_err(c, RL_E_INVALID, "gpu: rl_response_format: key over 64 bytes, NULL key with a length or reserved not zero");
+  if (n > c->cfg.max_batch || nq > c->cfg.max_requests)
+    return set_err(c, RL_E_CAPACITY, "gpu: verdict input exceeds configured max_batch/max_requests");
+  if (n && (!req_idx || !ans->match || !ans->code || !ans->limit_remaining || !ans->reset_s ||
+            !ans->requests_per_unit || !ans->unit))
+    return set_err(c, RL_E_INVALID, "gpu: null answer array");
+  std::vector<uint32_t> first((size_t)nq + 1, 0);
+  for (uint32_t d = 0; d < n; d++) {
+    if (req_idx[d] >= nq || (d && req_idx[d] < req_idx[d - 1]))
+      return set_err(c, RL_E_INVALID, "gpu: req_idx must be non-decreasing and below n_requests");
+    if (req_status && req_status[req_idx[d]] != RL_WIRE_OK)
+      return set_err(c, RL_E_INVALID, "gpu: a deferred or malformed request has no descriptors");
+    if (ans->reset_s[d] >= (1u << 21)) return set_err(c, RL_E_INVALID, "gpu: reset_s must be below 2^21");
+    first[req_idx[d] + 1]++;
+  }
+  for (uint32_t q = 0; q < nq; q++) first[q + 1] += first[q];
+  resp->resp_off[0] = 0;
+  if (!nq) return RL_OK;
+  const uint64_t bound = rlresp::bound(nq, n, rf);
+  if (!resp->bytes) return set_err(c, RL_E_INVALID, "gpu: rl_response_batch without bytes or resp_off");
+  if (bound > resp->bytes_cap || bound >= (1ull << 32))
+    return set_err(c, RL_E_CAPACITY, "gpu: rl_response_bound exceeds bytes_cap or 32 bits");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const VerdictLayout vl = verdict_layout(nq);
+  const RespLayout rl = resp_layout(nq, n, bound);
+  size_t need = 0;
+  auto piece = [&need](size_t bytes) {
+    const size_t o = need;
+    need += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
+    return o;
+  };
+  const size_t o_req = piece(n * 4ull), o_first = piece((nq + 1) * 4ull), o_status = piece(nq), o_match = piece(n),
+               o_code = piece(n), o_rem = piece(n * 4ull), o_reset = piece(n * 4ull), o_rpu = piece(n * 4ull),
+               o_unit = piece(n), o_verdict = piece(vl.bytes), o_resp = piece(rl.total);
+  uint8_t* B = nullptr;
+  HIPCHK(c, hipMalloc((void**)&B, need));
+  hipStream_t st = c->stream;
+  auto run = [&]() -> hipError_t {
+    hipError_t e = after_batches(c, st);
+    auto h2d = [&](size_t off, const void* src, size_t bytes) {
+      if (e == hipSuccess && bytes) e = hipMemcpyAsync(B + off, src, bytes, hipMemcpyHostToDevice, st);
+    };
+    h2d(o_req, req_idx, n * 4ull);
+    h2d(o_first, first.data(), (nq + 1) * 4ull);
+    if (req_status) h2d(o_status, req_status, nq);
+    h2d(o_match, ans->match, n);
+    h2d(o_code, ans->code, n);
+    h2d(o_rem, ans->limit_remaining, n * 4ull);
+    h2d(o_reset, ans->reset_s, n * 4ull);
+    h2d(o_rpu, ans->requests_per_unit, n * 4ull);
+    h2d(o_unit, ans->unit, n);
+    if (e != hipSuccess) return e;
+    const ReqOutDev ro{B + o_code, (uint32_t*)(B + o_rem), (uint32_t*)(B + o_reset), B + o_match, nullptr,
+                       (uint32_t*)(B + o_rpu), B + o_unit};
+    const VerdictDev vd = verdict_view(nq, n, opts, (const uint32_t*)(B + o_req), ro.match, ro.code, ro.rem, ro.reset,
+                                       ro.rpu, B + o_verdict);
+    e = launch_verdict(vd, B + o_verdict, st);
+    if (e != hipSuccess) return e;
+    if (req_status) launch_wire_code(B + o_status, B + o_verdict + vl.o_code, nq, st);
+    const RespDev rd = resp_view(nq, n, bound, (const uint32_t*)(B + o_req), (const uint32_t*)(B + o_first),
+                                 req_status ? B + o_status : nullptr, ro, B + o_verdict, B + o_resp);
+    e = launch_respond(rd, rf, st);
+    if (e != hipSuccess) return e;
+    e = hipMemcpyAsync(resp->resp_off, rd.resp_off, (nq + 1) * 4ull, hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) return e;
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return e;
+    const uint64_t total = std::min<uint64_t>(resp->resp_off[nq], bound);
+    if (total) e = hipMemcpyAsync(resp->bytes, rd.bytes, total, hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) return e;
+    return hipStreamSynchronize(st);
+  };
+  const hipError_t e = run();
+  (void)hipFree(B);
+  HIPCHK(c, e);
   return RL_OK;
 }
 

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rl_resp_emit.h"
+
 namespace rl {
 
 // One config node on the device (rl_config_node plus its child count).
@@ -212,6 +214,43 @@ void launch_wire_count(const WireDev& w, hipStream_t st);
 void launch_wire_emit(const WireDev& w, const WireOut& o, hipStream_t st);
 // overall_code[q] = 0 where status[q] != RL_WIRE_OK
 void launch_wire_code(const uint8_t* status, uint8_t* o_code, uint32_t n_req, hipStream_t st);
+
+// ---- serialized RateLimitResponse payloads written on the device (rl_resp.hip)
+// The answers and the verdict of one batch (device arrays) and the response
+// staging: soff and resp_off hold the sizes first and their exclusive scans
+// after launch_respond's scans. bytes is 4-byte aligned, cap bytes long.
+struct RespDev {
+  uint32_t n_req, n_desc, cap;
+  const uint32_t* req;          // [n_desc] each descriptor's request
+  const uint32_t* desc_first;   // [n_req + 1]
+  const uint8_t* status;        // [n_req] rl_wire_status, or null: every request RL_WIRE_OK
+  const uint8_t* code;
+  const uint32_t* rem;
+  const uint32_t* reset;
+  const uint8_t* match;
+  const uint32_t* rpu;
+  const uint8_t* unit;
+  const uint8_t* o_code;        // the verdict's outputs
+  const uint32_t* o_min;
+  const uint32_t* o_limit;
+  const uint32_t* o_rem;
+  const uint32_t* o_reset;
+  uint32_t* soff;               // [n_desc + 1] status bytes before each descriptor
+  uint32_t* resp_off;           // [n_req + 1]
+  uint8_t* bytes;
+  void* tmp;                    // the scans' temp storage (resp_scan_bytes)
+  size_t tmp_bytes;
+};
+struct RespLayout {
+  size_t soff, resp_off, tmp, bytes, total;
+  size_t tmp_bytes, cap;
+};
+// The staging of a batch of nq requests over n descriptors whose responses take at most `bound` bytes.
+RespLayout resp_layout(uint32_t nq, uint32_t n, uint64_t bound);
+// Enqueue: the size pass, the two scans, the emit pass. n_req != 0.
+hipError_t launch_respond(const RespDev& r, const rlresp::Format& fmt, hipStream_t st);
+// Enqueue the copy of bytes[0, min(resp_off[n_req], cap)) to dst (device-visible host memory).
+void launch_respond_to_host(const RespDev& r, uint8_t* dst, hipStream_t st);
 
 VerdictDev verdict_view(uint32_t n_req, uint32_t n_desc, uint32_t opts, const uint32_t* req, const uint8_t* match,
                         const uint8_t* code, const uint32_t* rem, const uint32_t* reset, const uint32_t* rpu,

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/ratelimit_hip.h"
+#include "rl_resp_emit.h"
 
 namespace rlpack {
 
@@ -472,6 +473,71 @@ int rl_request_batch_pack(const rl_request_batch* in, uint8_t* buf, uint64_t buf
   put(p.domain_bytes, in->domain_bytes, dom_total);
   put(p.entry_bytes, in->desc_bytes, ent_total);
   *out = p;
+  return RL_OK;
+}
+
+
+// ---- serialized RateLimitResponse payloads: the host twin of rl_resp.hip -----
+
+uint64_t rl_response_bound(uint32_t n_requests, uint32_t n_descriptors, const rl_response_format* fmt) {
+  rlresp::Format f;
+  if (!rlresp::format_from(fmt, &f)) return 0;
+  return rlresp::bound(n_requests, n_descriptors, f);
+}
+
+namespace {
+struct HostSink {
+  uint8_t* p;
+  void put(uint8_t b) { *p++ = b; }
+};
+}  // namespace
+
+// Two passes, like the device: the sizes into resp_off, then the bytes.
+int rl_response_serialize(uint32_t nq, const uint32_t* desc_first, const uint8_t* req_status,
+                          const rl_request_result* res, const rl_request_verdict* v, const rl_response_format* fmt,
+                          uint8_t* bytes, uint64_t bytes_cap, uint32_t* resp_off, uint64_t* bytes_needed) {
+  rlresp::Format f;
+  if (!desc_first || !v || !resp_off || !rlresp::format_from(fmt, &f)) return RL_E_INVALID;
+  if (desc_first[0]) return RL_E_INVALID;
+  const uint32_t n = desc_first[nq];
+  if (nq && !v->overall_code) return RL_E_INVALID;
+  if (nq && f.headers && (!v->min_descriptor || !v->header_limit || !v->header_remaining || !v->header_reset_s))
+    return RL_E_INVALID;
+  if (n && (!res || !res->code || !res->limit_remaining || !res->reset_s || !res->match || !res->requests_per_unit ||
+            !res->unit))
+    return RL_E_INVALID;
+  auto status = [res](uint32_t d) {
+    return rlresp::Status{res->code[d], res->match[d], res->requests_per_unit[d], res->unit[d],
+                          res->limit_remaining[d], res->reset_s[d]};
+  };
+  auto hdr = [&](uint32_t q) -> uint32_t {
+    if (!f.headers || desc_first[q + 1] == desc_first[q]) return 0;
+    return rlresp::headers_size(f, v->min_descriptor[q], v->header_limit[q], v->header_remaining[q],
+                                v->header_reset_s[q]);
+  };
+  uint64_t total = 0;
+  for (uint32_t q = 0; q < nq; q++) {
+    if (desc_first[q + 1] < desc_first[q]) return RL_E_INVALID;
+    if (req_status && req_status[q] != RL_WIRE_OK && desc_first[q + 1] != desc_first[q]) return RL_E_INVALID;
+  }
+  for (uint32_t q = 0; q < nq; q++) {
+    resp_off[q] = (uint32_t)total;
+    if (req_status && req_status[q] != RL_WIRE_OK) continue;
+    total += rlresp::head_size(v->overall_code[q]) + hdr(q);
+    for (uint32_t d = desc_first[q]; d < desc_first[q + 1]; d++) total += rlresp::status_size(status(d));
+    if (total >> 32) return RL_E_CAPACITY;  // (resp_off is 32-bit)
+  }
+  resp_off[nq] = (uint32_t)total;
+  if (bytes_needed) *bytes_needed = total;
+  if (total > bytes_cap || (total && !bytes)) return RL_E_CAPACITY;
+  HostSink s{bytes};
+  for (uint32_t q = 0; q < nq; q++) {
+    if (req_status && req_status[q] != RL_WIRE_OK) continue;
+    rlresp::emit_head(v->overall_code[q], s);
+    for (uint32_t d = desc_first[q]; d < desc_first[q + 1]; d++) rlresp::emit_status(status(d), s);
+    if (hdr(q))
+      rlresp::emit_headers(f, v->min_descriptor[q], v->header_limit[q], v->header_remaining[q], v->header_reset_s[q], s);
+  }
   return RL_OK;
 }
 

@@ -414,6 +414,106 @@ class Backend:
                                                    C.byref(v) if v is not None else None))
         return wr, r, v
 
+    @staticmethod
+    def response_bound(n_requests: int, n_descriptors: int, header_keys=None) -> int:
+        """rl_response_bound: no batch of that shape serializes to more bytes."""
+        f, _keep = abi.make_response_format(header_keys)
+        return int(lib().rl_response_bound(n_requests, n_descriptors, C.byref(f)))
+
+    def do_limit_wire_respond_async(self, wb: WireRequests, wire: dict, out: Optional[dict], verdict: Optional[dict],
+                                    resp: dict, header_keys=None, global_shadow: bool = False,
+                                    desc_cap: Optional[int] = None, bytes_cap: Optional[int] = None):
+        """rl_do_limit_wire_respond_async: do_limit_wire_async plus the serialized
+        RateLimitResponse payloads. ``resp``: ``bytes`` (uint8, from a PinnedArena;
+        ``bytes_cap`` defaults to its length) and ``resp_off`` (uint32 x (n + 1));
+        ``header_keys``: the (limit, remaining, reset) header names as bytes, or
+        None for no headers. ``out`` and ``verdict`` may both be None."""
+        wr = abi.RlWireResult()
+        for k in ("req_status", "desc_first", "n_descriptors"):
+            setattr(wr, k, abi.ptr(wire.get(k)))
+        r = v = None
+        if out is not None:
+            r = abi.RlRequestResult()
+            for k in out:
+                setattr(r, k, abi.ptr(out[k]))
+            if desc_cap is None:
+                desc_cap = min([len(a) for k, a in out.items() if k != "stats"] or [0])
+        wr.desc_cap = int(desc_cap or 0)
+        if verdict is not None:
+            v = abi.RlRequestVerdict()
+            for k in verdict:
+                setattr(v, k, abi.ptr(verdict[k]))
+        f, keep = abi.make_response_format(header_keys)
+        rb = abi.RlResponseBatch()
+        rb.bytes, rb.resp_off = abi.ptr(resp.get("bytes")), abi.ptr(resp.get("resp_off"))
+        rb.bytes_cap = len(resp["bytes"]) if bytes_cap is None else int(bytes_cap)
+        opts = abi.RL_VERDICT_OPT_GLOBAL_SHADOW if global_shadow else 0
+        self._check(self.L.rl_do_limit_wire_respond_async(self.ctx, C.byref(wb.struct), C.byref(wr),
+                                                           C.byref(r) if r is not None else None, opts,
+                                                           C.byref(v) if v is not None else None, C.byref(f),
+                                                           C.byref(rb)))
+        return wr, r, v, rb, keep
+
+    @staticmethod
+    def response_serialize(desc_first, req_status, res: dict, verdict: dict, header_keys=None):
+        """rl_response_serialize (host code): the per-descriptor answers ``res``
+        and the per-request ``verdict`` arrays -> (bytes, resp_off), request q's
+        serialized RateLimitResponse being bytes[resp_off[q]:resp_off[q + 1]]."""
+        L = lib()
+        first = np.ascontiguousarray(desc_first, np.uint32)
+        nq = len(first) - 1
+        st = None if req_status is None else np.ascontiguousarray(req_status, np.uint8)
+        keep = []
+        r = abi.RlRequestResult()
+        for k, dt in abi.REQUEST_RESULT_DTYPES.items():
+            if res.get(k) is not None:
+                keep.append(np.ascontiguousarray(res[k], dt))
+                setattr(r, k, abi.ptr(keep[-1]))
+        v = abi.RlRequestVerdict()
+        for k, dt in abi.REQUEST_VERDICT_DTYPES.items():
+            if verdict.get(k) is not None:
+                keep.append(np.ascontiguousarray(verdict[k], dt))
+                setattr(v, k, abi.ptr(keep[-1]))
+        f, fkeep = abi.make_response_format(header_keys)
+        off = np.zeros(nq + 1, np.uint32)
+        need = C.c_uint64(0)
+        rc = L.rl_response_serialize(nq, abi.ptr(first), abi.ptr(st), C.byref(r), C.byref(v), C.byref(f), None, 0,
+                                     abi.ptr(off), C.byref(need))
+        if rc not in (abi.RL_OK, abi.RL_E_CAPACITY):
+            raise RedisError("rl_response_serialize: malformed input [%s]" % abi.STATUS_NAMES.get(rc, rc), rc)
+        out = np.zeros(max(int(need.value), 1), np.uint8)
+        if rc:
+            rc = L.rl_response_serialize(nq, abi.ptr(first), abi.ptr(st), C.byref(r), C.byref(v), C.byref(f),
+                                         abi.ptr(out), int(need.value), abi.ptr(off), C.byref(need))
+            if rc:
+                raise RedisError("rl_response_serialize failed [%s]" % abi.STATUS_NAMES.get(rc, rc), rc)
+        return out[:int(need.value)], off
+
+    def debug_respond(self, n_requests, req_idx, answers: dict, header_keys=None, global_shadow: bool = False,
+                      req_status=None, bytes_cap: Optional[int] = None, out_bytes: Optional[np.ndarray] = None):
+        """rl_debug_respond: the device verdict and the device serializer on explicit
+        per-descriptor answers (``answers``: code, limit_remaining, reset_s, match,
+        requests_per_unit, unit) -> (bytes, resp_off)."""
+        req = np.ascontiguousarray(req_idx, np.uint32)
+        st = None if req_status is None else np.ascontiguousarray(req_status, np.uint8)
+        keep = []
+        r = abi.RlRequestResult()
+        for k, dt in abi.REQUEST_RESULT_DTYPES.items():
+            if answers.get(k) is not None:
+                keep.append(np.ascontiguousarray(answers[k], dt))
+                setattr(r, k, abi.ptr(keep[-1]))
+        f, fkeep = abi.make_response_format(header_keys)
+        if bytes_cap is None:
+            bytes_cap = self.response_bound(n_requests, len(req), header_keys)
+        out = np.zeros(max(bytes_cap, 1), np.uint8) if out_bytes is None else out_bytes
+        off = np.zeros(n_requests + 1, np.uint32)
+        rb = abi.RlResponseBatch()
+        rb.bytes, rb.bytes_cap, rb.resp_off = abi.ptr(out), bytes_cap, abi.ptr(off)
+        opts = abi.RL_VERDICT_OPT_GLOBAL_SHADOW if global_shadow else 0
+        self._check(self.L.rl_debug_respond(self.ctx, n_requests, len(req), abi.ptr(req), abi.ptr(st), C.byref(r), opts,
+                                             C.byref(f), C.byref(rb)))
+        return out, off
+
     def debug_verdict(self, n_requests, req_idx, match, code, limit_remaining, reset_s, requests_per_unit,
                       global_shadow: bool = False) -> dict:
         """rl_debug_verdict: the device verdict alone on explicit per-descriptor answers."""
@@ -806,11 +906,15 @@ class GpuRateLimitService:
 
     def __init__(self, config_files, near_limit_ratio: float = 0.8, local_cache: bool = False,
                  cache_key_prefix: str = "", per_second: bool = False, global_shadow_mode: bool = False,
-                 **backend_kw):
+                 header_keys=None, **backend_kw):
         from .config import ConfigTree
         self.interner = RuleInterner()
         self.tree = ConfigTree.from_yaml(config_files, cache_key_prefix, self.interner)
         self.global_shadow_mode = global_shadow_mode
+        # the (limit, remaining, reset) header names of should_rate_limit_responses_pipelined's
+        # serialized responses (settings HeaderRatelimitLimit / -Remaining / -Reset); None: no headers
+        self.header_keys = None if header_keys is None else tuple(
+            k.encode() if isinstance(k, str) else bytes(k) for k in header_keys)
         self.backend = Backend(near_limit_ratio, local_cache, per_second, **backend_kw)
         self.backend.load_config(self.tree)
         self.stats = {}  # stats key -> [6 counters] (the gostats store)
@@ -957,6 +1061,84 @@ class GpuRateLimitService:
                 for q, v in zip(deferred, vs):
                     answers[b][0][q] = v
                 answers[b][1] += shadow
+            return [tuple(x) for x in answers]
+        finally:
+            if packer is not None:
+                packer.close()
+            if self.backend.ctx:
+                try:
+                    self.backend.synchronize()  # (a failed flight: nothing may still write into the arena)
+                except RedisError:
+                    pass
+            arena.close()
+
+    def should_rate_limit_responses_pipelined(self, batches):
+        """``batches``: a list of (payloads, nows) as for
+        should_rate_limit_payloads_pipelined. Payload bytes in, payload bytes
+        out: every batch goes through ``rl_do_limit_wire_respond_async`` and
+        comes back as serialized RateLimitResponse messages, written on the
+        device; per-descriptor arrays never cross PCIe. The deferred messages
+        are resubmitted through ``RequestPacker`` and the packed path as there
+        and serialized on the host (``rl_response_serialize``). -> per batch
+        ([response bytes per request], this batch's global-shadow count), a
+        malformed message's entry being a RedisError (that request's alone)."""
+        from .config import RequestPacker, batch_arrays
+        arena = PinnedArena()
+        packer = None
+        hk = self.header_keys
+        try:
+            n_rules = max(len(self.interner.keys), 1)
+            max_batch = int(self.backend.cfg.max_batch)
+            flight = []
+            for msgs, nows in batches:
+                wb = self.backend.wire_batch(msgs, nows, arena, n_rules)
+                nq = len(msgs)
+                cap = max(min(max_batch, wb.msgs_bytes // 2), 1)  # (a descriptor takes 2 payload bytes at least)
+                out = {"stats": arena.array(n_rules * abi.RL_NUM_STATS, np.uint64)}
+                ver = {"global_shadow": arena.array(1, np.uint64)}
+                ver["global_shadow"][0] = 0
+                wire = {"req_status": arena.array(nq, np.uint8)}
+                resp = {"bytes": arena.array(self.backend.response_bound(nq, cap, hk), np.uint8),
+                        "resp_off": arena.array(nq + 1, np.uint32)}
+                keep = self.backend.do_limit_wire_respond_async(wb, wire, out, ver, resp, hk, self.global_shadow_mode,
+                                                                cap)  # (out holds the stats alone)
+                flight.append((wb, wire, out, ver, resp, keep))
+            self.backend.synchronize()
+            answers = []
+            again = []  # (batch, its deferred messages' indices)
+            for b, (wb, wire, out, ver, resp, _) in enumerate(flight):
+                nq = wb.n_requests
+                self._add_stats(out["stats"][:n_rules * abi.RL_NUM_STATS])
+                shadow = int(ver["global_shadow"][0])
+                self.global_shadow_count += shadow
+                off = resp["resp_off"][:nq + 1]
+                raw = resp["bytes"][:int(off[nq])].tobytes()
+                rs = [raw[int(off[q]):int(off[q + 1])] for q in range(nq)]
+                status = wire["req_status"][:nq]
+                for q in np.nonzero(status == abi.RL_WIRE_MALFORMED)[0]:
+                    rs[q] = RedisError("gpu: malformed RateLimitRequest", abi.RL_E_INVALID)
+                deferred = np.nonzero(status == abi.RL_WIRE_DEFERRED)[0]
+                if len(deferred):
+                    again.append((b, deferred))
+                answers.append([rs, shadow])
+            for b, deferred in again:
+                msgs, nows = batches[b]
+                if packer is None:
+                    packer = RequestPacker(len(self.interner.keys))
+                rb = packer.pack([msgs[q] for q in deferred], [nows[q] for q in deferred])
+                a = batch_arrays(rb)
+                nr = max(packer.rules(), 1)
+                res = self.backend.do_limit_requests_verdict(a, nr, self.global_shadow_mode, True)
+                keys = self.interner.keys + [packer.rule_key(i) for i in range(len(self.interner.keys), nr)]
+                self._add_stats(res["stats"], keys)
+                self.global_shadow_count += res["global_shadow"]
+                first = np.zeros(len(deferred) + 1, np.uint32)
+                np.cumsum(np.bincount(a["req_idx"], minlength=len(deferred)), out=first[1:])
+                raw, off = self.backend.response_serialize(first, None, res, res, hk)
+                raw = raw.tobytes()
+                for i, q in enumerate(deferred):
+                    answers[b][0][q] = raw[int(off[i]):int(off[i + 1])]
+                answers[b][1] += res["global_shadow"]
             return [tuple(x) for x in answers]
         finally:
             if packer is not None:

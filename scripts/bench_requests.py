@@ -31,8 +31,18 @@ rl_request_batch_pack on each batch's messages, split over --pack-threads N
 copies the payload bytes into its pinned buffer and writes the offsets and
 clocks.
 
+--respond (with --path wire-async) takes the answers back as serialized
+RateLimitResponse payloads written on the GPU (rl_do_limit_wire_respond_async)
+instead of the per-descriptor and per-request arrays: out carries the stats
+alone and verdict is NULL in the timed loop. The warm-up batches return both
+and check the device's bytes against rl_response_serialize over the arrays;
+that host step is then timed on 1, 4 and 16 threads (one contiguous slice of
+the requests per thread): it is what the device spares the host.
+--respond-headers is --respond with the three RateLimit-* header names
+configured, so that every response also carries its three HeaderValues.
+
     python scripts/bench_requests.py [--config c1|c2] [--steps K] [--verdict off|full|only]
-                                     [--path sync|packed-async|wire-async]
+                                     [--path sync|packed-async|wire-async] [--respond | --respond-headers]
                                      [--from-payloads [--pack-threads N]]
 """
 import argparse
@@ -51,6 +61,7 @@ from ratelimit_amd.config import ConfigTree  # noqa: E402
 from ratelimit_amd.limiter import Backend, PinnedArena  # noqa: E402
 
 PACKED_RING = 8  # packed buffers (and output sets) in rotation on --path packed-async
+HEADER_KEYS = (b"RateLimit-Limit", b"RateLimit-Remaining", b"RateLimit-Reset")  # --respond-headers
 
 
 def pinned(a):
@@ -73,7 +84,13 @@ def main():
     ap.add_argument("--path", default="sync", choices=["sync", "packed-async", "wire-async"])
     ap.add_argument("--from-payloads", action="store_true")
     ap.add_argument("--pack-threads", type=int, default=1)
+    ap.add_argument("--respond", action="store_true")
+    ap.add_argument("--respond-headers", action="store_true")
     args = ap.parse_args()
+    args.respond = args.respond or args.respond_headers
+    keys = HEADER_KEYS if args.respond_headers else None
+    if args.respond and (args.path != "wire-async" or args.from_payloads):
+        ap.error("--respond goes with --path wire-async (buffers built in advance)")
     if args.from_payloads and args.path == "sync":
         ap.error("--from-payloads goes with --path packed-async or wire-async")
     if not 1 <= args.pack_threads <= 16:
@@ -172,20 +189,68 @@ def main():
                 ver = {k: arena.array(nq, dt) for k, dt in abi.REQUEST_VERDICT_DTYPES.items()}
                 ver["global_shadow"] = arena.array(1, np.uint64)
             wire = {"req_status": arena.array(nq, np.uint8), "n_descriptors": arena.array(1, np.uint32)}
+            resp = None
+            if args.respond:
+                if out is None or ver is None:
+                    ap.error("--respond: the warm-up compares with the arrays (--verdict full)")
+                wire["desc_first"] = arena.array(nq + 1, np.uint32)
+                resp = {"bytes": arena.array(be_req.response_bound(nq, n, keys), np.uint8),
+                        "resp_off": arena.array(nq + 1, np.uint32)}
             ws = wb.struct
             ring.append((wb, out, ver, wb.buf[ws.now:ws.now + 4 * nq].view(np.uint32), wire,
                          wb.buf[ws.msg_off:ws.msg_off + 4 * (nq + 1)].view(np.uint32),
-                         wb.buf[ws.msgs:ws.msgs + ws.msgs_bytes]))
+                         wb.buf[ws.msgs:ws.msgs + ws.msgs_bytes], resp))
     L_msg = payloads[0].shape[1] if payloads else 0
     msg_off32 = (np.arange(nq + 1, dtype=np.uint64) * L_msg).astype(np.uint32)
 
-    def wire_call(j, now, b=None):
-        wb, out, ver, now32, wire, off32, body = ring[j]
+    def wire_call(j, now, b=None, arrays=False):
+        wb, out, ver, now32, wire, off32, body, resp = ring[j]
         if b is not None:  # --from-payloads: the host's work per batch
             body[:] = payloads[b].reshape(-1)
             off32[:] = msg_off32
         now32[:] = now
+        if resp is not None:  # the timed loop takes the responses alone (and the stats); the warm-up the arrays too
+            return be_req.do_limit_wire_respond_async(wb, wire, out if arrays else {"stats": out["stats"]},
+                                                      ver if arrays else None, resp, keys, False, n)
         return be_req.do_limit_wire_async(wb, wire, out, ver, False, n)
+
+    def host_serialize(j, threads, reps=5):
+        """rl_response_serialize over ring[j]'s arrays, one contiguous slice of the requests per thread
+        -> [seconds] per repetition."""
+        from concurrent.futures import ThreadPoolExecutor
+        L = lib()
+        _, out, ver, _, wire, _, _, resp = ring[j]
+        first = wire["desc_first"][:nq + 1]
+        f, keep = abi.make_response_format(keys)
+        jobs = []
+        for k in range(threads):
+            q0, q1 = nq * k // threads, nq * (k + 1) // threads
+            d0 = int(first[q0])
+            r, v = abi.RlRequestResult(), abi.RlRequestVerdict()
+            for key in abi.REQUEST_RESULT_DTYPES:
+                setattr(r, key, abi.ptr(out[key][d0:]))
+            for key in abi.REQUEST_VERDICT_DTYPES:
+                setattr(v, key, abi.ptr(ver[key][q0:]))
+            fs = (first[q0:q1 + 1] - first[q0]).astype(np.uint32)
+            cap = be_req.response_bound(q1 - q0, int(fs[-1]), keys)
+            jobs.append((q1 - q0, fs, r, v, np.zeros(cap, np.uint8), cap, np.zeros(q1 - q0 + 1, np.uint32),
+                         C.c_uint64(0)))
+
+        def one(job):
+            m, fs, r, v, buf, cap, off, need = job
+            rc = L.rl_response_serialize(m, abi.ptr(fs), None, C.byref(r), C.byref(v), C.byref(f), abi.ptr(buf), cap,
+                                         abi.ptr(off), C.byref(need))
+            assert rc == 0, rc
+            return int(need.value)
+
+        times = []
+        with ThreadPoolExecutor(threads) as ex:
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                total = sum(ex.map(one, jobs))
+                times.append(time.perf_counter() - t0)
+        assert total == int(resp["resp_off"][nq])
+        return times
 
     # --from-payloads on packed-async: each batch's messages split over the pack threads, every slice
     # parsed (rl_packer_pack) and laid out (rl_request_batch_pack) by its thread, then submitted
@@ -263,6 +328,8 @@ def main():
             packed_from_payloads(s % PACKED_RING, s % 4, W.NOW0 + s)
         elif args.from_payloads:
             wire_call(s % PACKED_RING, W.NOW0 + s, s % 4)
+        elif args.respond:
+            wire_call(s % PACKED_RING, W.NOW0 + s, arrays=True)
         else:
             async_call(s % PACKED_RING, W.NOW0 + s)
         be_req.synchronize()
@@ -280,6 +347,12 @@ def main():
         if args.path == "wire-async":
             wire = ring[s % PACKED_RING][4]
             assert not wire["req_status"].any() and int(wire["n_descriptors"][0]) == n
+        if args.respond:  # the device's bytes are the host twin's over the returned arrays
+            resp = ring[s % PACKED_RING][7]
+            raw, off = be_req.response_serialize(wire["desc_first"][:nq + 1], None, out, ver, keys)
+            assert np.array_equal(off, resp["resp_off"][:nq + 1]), "resp_off"
+            assert np.array_equal(raw, resp["bytes"][:len(raw)]), "response bytes"
+            d2h = len(raw) + 4 * (nq + 1)  # the responses and their offsets
         if out is not None:
             for k in ("code", "limit_remaining", "reset_s"):
                 assert np.array_equal(out[k], pr[k]), k
@@ -289,6 +362,10 @@ def main():
             want = np.ones(nq, np.uint8)
             np.maximum.at(want, batches[s % 4][0]["req_idx"], pr["code"])
             assert np.array_equal(ver["overall_code"], want), "overall_code"
+    host_ms = resp_bytes = None
+    if args.respond:  # the host step the device replaces, on the last warm-up batch's arrays
+        resp_bytes = int(ring[7 % PACKED_RING][7]["resp_off"][nq])
+        host_ms = {str(t): [round(1e3 * x, 3) for x in host_serialize(7 % PACKED_RING, t)] for t in (1, 4, 16)}
     res = {}
     if args.path != "sync":
         base = be_req.batch_progress()[0]
@@ -323,7 +400,7 @@ def main():
     if args.path == "packed-async":
         path = "rl_do_limit_requests_packed_async"
     if args.path == "wire-async":
-        path = "rl_do_limit_wire_async"
+        path = "rl_do_limit_wire_respond_async" if args.respond else "rl_do_limit_wire_async"
     out = {"path": path + " (host buffers, PCIe-inclusive)", "config": args.config.upper(),
            "verdict": args.verdict, "d2h_bytes_per_descriptor": d2h / n,
            "descriptors_per_batch": n, "steps": args.steps,
@@ -342,6 +419,11 @@ def main():
         out["from_payloads"] = bool(args.from_payloads)
         if pack_ring:
             out["pack_threads"] = NT
+    if args.respond:
+        out["respond"] = True
+        out["response_headers"] = bool(args.respond_headers)
+        out["response_bytes_per_descriptor"] = resp_bytes / n
+        out["host_serialize_ms"] = host_ms  # rl_response_serialize per batch on 1, 4, 16 threads, each repetition
     print(json.dumps(out))
 
 
