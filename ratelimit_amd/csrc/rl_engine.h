@@ -163,6 +163,9 @@ struct Engine {
   uint32_t* h_late = nullptr;  // pinned [NBUF]: k_late met a long run (RUN_FAST) in this buffer's batch
   uint32_t late_recent = 0;    // batches left with k_late's full long-run grid
   int late_mode = 1;           // RL_LATE_CUE: 0 full grid always, 1 while recent batches had long runs
+  uint32_t* h_list = nullptr;  // pinned [NBUF]: k_run_check found this buffer's batch sparse (few keys seen once)
+  uint32_t list_recent = 0;    // batches left with the keys-seen-once list built
+  int list_mode = 1;           // RL_LIST_CUE: 0 list always built, 1 while recent batches were sparse, 2 never
   unsigned long long* h_counters = nullptr;
   std::string last_error;
   uint64_t batches = 0, decisions = 0;

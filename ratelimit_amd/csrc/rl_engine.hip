@@ -198,25 +198,41 @@ uint32_t enqueue(Engine* c, const BatchDev& b_in, const OutDev& o, int restore, 
     if (c->late_recent) c->late_recent--;
   }
   uint32_t* lhint = c->late_mode == 1 ? c->h_late + k : nullptr;
+  // the keys-seen-once list (Scratch::uniq): built while recent batches were
+  // sparse (hot keys: C2, C2U), where k_table walks it; a batch of mostly
+  // distinct keys (C1, C3) is answered in arrival order and never opens it,
+  // so its stage A skips the bookkeeping and the 8 B per key. A sparse batch
+  // that arrives with the list off is answered in arrival order too.
+  bool list_on = c->list_mode == 0;
+  if (c->list_mode == 1) {
+    for (uint32_t j = 0; j < NBUF; j++)
+      if (__atomic_load_n(&c->h_list[j], __ATOMIC_RELAXED)) {
+        __atomic_store_n(&c->h_list[j], 0u, __ATOMIC_RELAXED);
+        c->list_recent = 4 * NBUF;
+      }
+    list_on = c->list_recent > 0;
+    if (c->list_recent) c->list_recent--;
+  }
+  uint32_t* uhint = c->list_mode == 1 ? c->h_list + k : nullptr;
   if (pipelined) {
     hipStream_t a = c->pipe[k];
     hipEvent_t* ev = prof_events(c);
     (void)hipStreamWaitEvent(a, c->b_done[k], 0);    // buffer k's previous batch is done
     (void)hipStreamWaitEvent(a, c->consumed[k], 0);  // ... and its routed results were read
-    launch_stage_a(b, c->s[k], isolate, P.per_second, a, ev, hint, lng, bhint, big_full);
+    launch_stage_a(b, c->s[k], isolate, P.per_second, a, ev, hint, lng, bhint, big_full, uhint, list_on);
     if (early) launch_b_begin_early(b, o, c->s[k], restore, a, c->log_ctr);  // (off the table-order chain)
     (void)hipStreamWaitEvent(a, c->b_table[c->last], 0);  // table order (not the previous k_finish)
     launch_stage_b(b, o, t, P, c->s[k], restore, a, ev, errb_prev, c->b_table[k], ev ? c->d_kt_acc : nullptr,
-                   early, lhint, late_full);
+                   early, lhint, late_full, list_on);
     (void)hipEventRecord(c->b_done[k], a);
   } else {
     if (!st) st = c->stream;
     (void)after_batches(c, st);
     hipEvent_t* ev = prof_events(c);
-    launch_stage_a(b, c->s[k], isolate, P.per_second, st, ev, hint, lng, bhint, big_full);
+    launch_stage_a(b, c->s[k], isolate, P.per_second, st, ev, hint, lng, bhint, big_full, uhint, list_on);
     if (early) launch_b_begin_early(b, o, c->s[k], restore, st, c->log_ctr);
     launch_stage_b(b, o, t, P, c->s[k], restore, st, ev, errb_prev, c->b_table[k], ev ? c->d_kt_acc : nullptr,
-                   early, lhint, late_full);
+                   early, lhint, late_full, list_on);
     (void)hipEventRecord(c->b_done[k], st);
   }
   c->last = k;
@@ -514,6 +530,9 @@ Engine* eng_create(const rl_config* cfg_in, char* err, size_t errlen) {
   ok = ok && hipHostMalloc((void**)&c->h_late, NBUF * sizeof(uint32_t)) == hipSuccess;
   if (ok) memset(c->h_late, 0, NBUF * sizeof(uint32_t));
   if (const char* lc = getenv("RL_LATE_CUE")) c->late_mode = atoi(lc);  // (A/B knob)
+  ok = ok && hipHostMalloc((void**)&c->h_list, NBUF * sizeof(uint32_t)) == hipSuccess;
+  if (ok) memset(c->h_list, 0, NBUF * sizeof(uint32_t));
+  if (const char* uc = getenv("RL_LIST_CUE")) c->list_mode = atoi(uc);  // (A/B knob)
   if (!ok) return fail("gpu: device allocation failed (table_slots/arena/max_batch too large?)", c);
   ok = hipMemsetAsync(c->slots, 0, c->nslots * sizeof(Slot), c->stream) == hipSuccess &&
        hipMemsetAsync(c->log_ctr, 0, (size_t)(LOG_PARTS + 1) * LOG_CTR_STRIDE * 8, c->stream) == hipSuccess &&
@@ -617,6 +636,7 @@ void eng_destroy(Engine* c) {
   if (c->h_long) (void)hipHostFree(c->h_long);
   if (c->h_big) (void)hipHostFree(c->h_big);
   if (c->h_late) (void)hipHostFree(c->h_late);
+  if (c->h_list) (void)hipHostFree(c->h_list);
   for (void* p : {(void*)c->cfg_blob, (void*)c->mbuf})
     if (p) (void)hipFree(p);
   if (c->h_match) (void)hipHostFree(c->h_match);

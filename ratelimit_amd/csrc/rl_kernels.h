@@ -268,10 +268,17 @@ struct Scratch {
 // when it queues a bucket too large for its LDS (hot keys); big_full: the
 // large-bucket kernels get their full grids (else one workgroup each: they are
 // grid-stride, so a batch with a large bucket the host did not expect is
-// still answered, more slowly; C1 never has one)
+// still answered, more slowly; C1 never has one). list_hint: a host word
+// k_run_check sets when the batch is sparse (fewer than 3/4 of its
+// descriptors outside the sorted order); list_on: the stage-A kernels build
+// the keys-seen-once list (Scratch::uniq) for this batch. The same list_on
+// goes to the batch's launch_stage_b: with it k_table chooses between the
+// list and arrival order per batch, without it it takes arrival order and
+// reads neither the list nor its count.
 void launch_stage_a(const BatchDev& b, const Scratch& s, int isolate, int per_second, hipStream_t st,
                     hipEvent_t* ev = nullptr, uint32_t* long_hint = nullptr, bool long_kernel = false,
-                    uint32_t* big_hint = nullptr, bool big_full = true);
+                    uint32_t* big_hint = nullptr, bool big_full = true, uint32_t* list_hint = nullptr,
+                    bool list_on = true);
 // errb_prev: the previous batch's table-stage word (this batch's starts from
 // it); table_done (optional) is recorded once the table kernels are done, before
 // k_finish: the next batch's stage B waits for it, not for k_finish.
@@ -283,7 +290,7 @@ void launch_stage_a(const BatchDev& b, const Scratch& s, int isolate, int per_se
 void launch_stage_b(const BatchDev& b, const OutDev& o, const TableDev& t, const Params& P, const Scratch& s,
                     int restore, hipStream_t st, hipEvent_t* ev, const uint32_t* errb_prev, hipEvent_t table_done,
                     unsigned long long* kt_acc = nullptr, bool early = false, uint32_t* late_hint = nullptr,
-                    bool late_full = true);
+                    bool late_full = true, bool list_on = true);
 void launch_b_begin_early(const BatchDev& b, const OutDev& o, const Scratch& s, int restore, hipStream_t st,
                           const unsigned long long* log_ctr);
 // ev (optional, RL_NUM_STAGES + 1 events on stream st): recorded before

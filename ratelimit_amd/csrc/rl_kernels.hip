@@ -1936,7 +1936,10 @@ __device__ inline void lds_sort3(BucketLds<B>& L, uint32_t (&kk)[B::ITEMS], uint
 // exclusive prefix. Every gather is an unconditional load at a clamped
 // position, issued in a straight-line loop before any use, so all of a lane's
 // loads are in flight together (a load under a branch is waited for on the spot).
-template <typename B, bool FROM_LDS>
+// PRE: the caller reserved the run ids and the dup-run entries already (L.rb,
+// L.db, L.nruns set, L.dcnt / L.carry / L.hcarry cleared, behind a barrier):
+// no counting pass and no reservation here.
+template <typename B, bool FROM_LDS, bool PRE = false>
 __device__ inline void bucket_segment(BucketLds<B>& L, uint32_t d, uint32_t S, uint32_t base,
                                       const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sh,
                                       uint32_t* __restrict__ segsum, uint32_t* __restrict__ rid,
@@ -1949,7 +1952,7 @@ __device__ inline void bucket_segment(BucketLds<B>& L, uint32_t d, uint32_t S, u
   // runs of the bucket -> run id base; runs of two or more (counted at their
   // second element) -> their place in the dup-run list k_table works through
   uint32_t nh = 0, nd = 0;
-  for (uint32_t c0 = 0; c0 < S; c0 += B::CAP) {
+  for (uint32_t c0 = 0; !PRE && c0 < S; c0 += B::CAP) {
     uint32_t a[IT], b[IT], c[IT];
 #pragma unroll
     for (uint32_t i = 0; i < IT; i++) {
@@ -1965,19 +1968,21 @@ __device__ inline void bucket_segment(BucketLds<B>& L, uint32_t d, uint32_t S, u
       nd += (p < S && p >= 1 && a[i] == b[i] && (p == 1 || c[i] != a[i])) ? 1u : 0u;
     }
   }
-  nh = block_sum(L, nh);
-  nd = block_sum(L, nd);
-  BK_STAMP(d, 4);
-  if (tid == 0) {
-    const unsigned long long old = atomicAdd(num_runs, ((unsigned long long)nd << 32) | nh);
-    L.rb = (uint32_t)old;
-    L.db = (uint32_t)(old >> 32);
-    L.dcnt = 0;
-    L.nruns = nh;
-    L.carry = SegPair{0, 0};
-    L.hcarry = 0;
+  if constexpr (!PRE) {
+    nh = block_sum(L, nh);
+    nd = block_sum(L, nd);
+    BK_STAMP(d, 4);
+    if (tid == 0) {
+      const unsigned long long old = atomicAdd(num_runs, ((unsigned long long)nd << 32) | nh);
+      L.rb = (uint32_t)old;
+      L.db = (uint32_t)(old >> 32);
+      L.dcnt = 0;
+      L.nruns = nh;
+      L.carry = SegPair{0, 0};
+      L.hcarry = 0;
+    }
+    __syncthreads();
   }
-  __syncthreads();
   const uint32_t rb = L.rb;
   for (uint32_t c0 = 0; c0 < S; c0 += B::CAP) {
     const uint32_t s0 = c0 + wave * B::STRIP;
@@ -2121,6 +2126,13 @@ __device__ inline void sample_heavy(BucketLds<B>& L, uint32_t S, uint32_t ntiles
   __syncthreads();
 }
 
+#ifndef RL_BK_EARLY
+#define RL_BK_EARLY 1  // (A/B builds: 0 = bucket_segment counts and reserves the runs after the sort)
+#endif
+// LIST: the keys seen once are listed for k_table's singleton part (a batch
+// the host expects to be sparse: launch_stage_a); without it they are only
+// left out of the sorted order, and k_table answers them in arrival order.
+template <bool LIST>
 __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
     const uint4* __restrict__ pt,
     const uint32_t* __restrict__ info, uint32_t ntiles, uint32_t* __restrict__ sk, uint32_t* __restrict__ sv,
@@ -2183,9 +2195,9 @@ __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
   // keys finds the duplicated ones (~5% at C1), and only those are sorted,
   // segmented and written. Their sorted positions are one block per bucket,
   // allocated from sorted_n (runs never cross buckets, so no order between
-  // buckets is needed). The keys seen once are listed, bucket by bucket, for
-  // k_table's singleton part: their home slots share the bucket's top 10
-  // bits, so a workgroup walking the list probes 1/1024 of the table.
+  // buckets is needed). With LIST the keys seen once are listed, bucket by
+  // bucket, for k_table's singleton part: their home slots share the bucket's
+  // top 10 bits, so a workgroup walking the list probes 1/1024 of the table.
   uint32_t* ht = L.v;                                   // [2 CAP]: L.v and L.h (values are in registers)
   uint8_t* df = reinterpret_cast<uint8_t*>(&L.wcnt[0][0]);  // [CAP] duplicated-key flag per position
   static_assert(sizeof(L.wcnt) >= B::CAP, "dup flags fit the multisplit rows");
@@ -2199,6 +2211,7 @@ __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
   for (uint32_t j = tid; j < HT; j += B::THREADS) ht[j] = 0xFFFFFFFFu;
   for (uint32_t j = tid; j < B::CAP / 4; j += B::THREADS) reinterpret_cast<uint32_t*>(df)[j] = 0u;
   __syncthreads();
+  uint32_t win = 0;  // bit i: item i was the first of its key in the bucket (it owns the key's ht entry)
 #pragma unroll
   for (uint32_t i = 0; i < B::ITEMS; i++) {
     const uint32_t p = strip0 + i * 64 + lane;
@@ -2206,8 +2219,11 @@ __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
     uint32_t h = (kk[i] * 0x9E3779B1u) >> HT_SHIFT;
     for (;;) {  // (S <= CAP = HT / 2: a free entry is always found)
       const uint32_t o = atomicCAS(&ht[h], 0xFFFFFFFFu, p);
-      if (o == 0xFFFFFFFFu) break;  // first of its key in the bucket
-      if (L.k[o] == kk[i]) {        // seen before: both are duplicated
+      if (o == 0xFFFFFFFFu) {  // first of its key in the bucket
+        win |= 1u << i;
+        break;
+      }
+      if (L.k[o] == kk[i]) {  // seen before: both are duplicated
         df[p] = 1;
         df[o] = 1;
         break;
@@ -2217,32 +2233,41 @@ __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
   }
   __syncthreads();
   // compact the duplicated elements, keeping the bucket (= arrival) order,
-  // and rank the keys seen once for the list
+  // count their keys (a key's first element that got the flag: the runs of
+  // the sorted order, each of two or more) and, with LIST, rank the keys seen
+  // once for the list
   const uint64_t lt = (1ull << lane) - 1;
-  uint32_t cidx[B::ITEMS], sidx[B::ITEMS], wc = 0, ws = 0, dmask = 0, smask = 0;
+  uint32_t cidx[B::ITEMS], sidx[LIST ? B::ITEMS : 1], wc = 0, ws = 0, wr = 0, dmask = 0, smask = 0;
 #pragma unroll
   for (uint32_t i = 0; i < B::ITEMS; i++) {
     const uint32_t p = strip0 + i * 64 + lane;
-    const bool dup = p < S && df[p], one = p < S && !df[p];
-    const uint64_t bl = __ballot(dup), bs = __ballot(one);
+    const bool dup = p < S && df[p];
+    const uint64_t bl = __ballot(dup);
     cidx[i] = wc + (uint32_t)__popcll(bl & lt);
-    sidx[i] = ws + (uint32_t)__popcll(bs & lt);
     wc += (uint32_t)__popcll(bl);
-    ws += (uint32_t)__popcll(bs);
     dmask |= dup ? 1u << i : 0u;
-    smask |= one ? 1u << i : 0u;
+    if (RL_BK_EARLY) wr += (uint32_t)__popcll(__ballot(dup && ((win >> i) & 1u)));
+    if constexpr (LIST) {
+      const bool one = p < S && !df[p];
+      const uint64_t bs = __ballot(one);
+      sidx[i] = ws + (uint32_t)__popcll(bs & lt);
+      ws += (uint32_t)__popcll(bs);
+      smask |= one ? 1u << i : 0u;
+    }
   }
   if (lane == 0) {
     L.wsum[wave] = wc;
-    L.lw[wave] = ws;
+    L.sh[wave] = wr;
+    if (LIST) L.lw[wave] = ws;
   }
   __syncthreads();
-  uint32_t wpre = 0, M = 0, spre = 0;
+  uint32_t wpre = 0, M = 0, spre = 0, nh = 0;
 #pragma unroll
   for (uint32_t w = 0; w < B::WAVES; w++) {
     wpre += w < wave ? L.wsum[w] : 0u;
-    spre += w < wave ? L.lw[w] : 0u;
+    if (LIST) spre += w < wave ? L.lw[w] : 0u;
     M += L.wsum[w];
+    nh += L.sh[w];
   }
 #pragma unroll
   for (uint32_t i = 0; i < B::ITEMS; i++) {
@@ -2252,17 +2277,28 @@ __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
     L.v[c] = vv[i];
     L.h[c] = hh[i];
   }
+  // One round of reservations, all issued together by thread 0: the sorted
+  // block, the run ids with the dup-run entries (every run here has two or
+  // more elements: as many entries as runs) and, with LIST, the list block.
+  // The first two are not needed before the sort is done: they stay in
+  // thread 0's registers until then.
+  uint32_t r_base = 0;
+  unsigned long long r_runs = 0;
   if (tid == 0) {
-    if (M) L.base_pos = atomicAdd(sorted_n, M);
-    L.ub = M < S ? atomicAdd(uniq_n, S - M) : 0u;
+    if (M) {
+      r_base = atomicAdd(sorted_n, M);
+      if (RL_BK_EARLY) r_runs = atomicAdd(num_runs, ((unsigned long long)nh << 32) | nh);
+    }
+    if constexpr (LIST) L.ub = M < S ? atomicAdd(uniq_n, S - M) : 0u;
   }
   __syncthreads();
-  const uint32_t ub = L.ub + spre;
+  if constexpr (LIST) {
+    const uint32_t ub = L.ub + spre;
 #pragma unroll
-  for (uint32_t i = 0; i < B::ITEMS; i++)
-    if ((smask >> i) & 1u) uniq[ub + sidx[i]] = make_uint2(vv[i], kk[i]);
+    for (uint32_t i = 0; i < B::ITEMS; i++)
+      if ((smask >> i) & 1u) uniq[ub + sidx[i]] = make_uint2(vv[i], kk[i]);
+  }
   if (!M) return;  // (uniform) every key of the bucket is seen once
-  const uint32_t base = L.base_pos;
   if (M <= 64) {
     // one wave: stable rank of (key, compact index) by comparisons
     if (wave == 0) {
@@ -2279,7 +2315,6 @@ __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
         L.h[r] = y;
       }
     }
-    __syncthreads();
   } else {
 #pragma unroll
     for (uint32_t i = 0; i < B::ITEMS; i++) {
@@ -2291,12 +2326,28 @@ __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
     __syncthreads();
     lds_sort3(L, kk, vv, hh, M);
   }
+  if (tid == 0) {
+    L.base_pos = r_base;
+    if (RL_BK_EARLY) {
+      L.rb = (uint32_t)r_runs;
+      L.db = (uint32_t)(r_runs >> 32);
+      L.dcnt = 0;
+      L.nruns = nh;
+      L.carry = SegPair{0, 0};
+      L.hcarry = 0;
+    }
+  }
+  __syncthreads();
+  const uint32_t base = L.base_pos;
   for (uint32_t p = tid; p < M; p += B::THREADS) {
     sk[base + p] = L.k[p];
     sv[base + p] = L.v[p];
   }
   BK_STAMP(d, 3);
-  bucket_segment<B, true>(L, d, M, base, sk, sh, segsum, rid, run_start, run_end, num_runs, drun);
+  // (inlined by force: with two instantiations of this kernel calling it, the
+  // inliner leaves it a real call, at 120 VGPRs and a stack frame)
+  [[clang::always_inline]] bucket_segment<B, true, RL_BK_EARLY != 0>(L, d, M, base, sk, sh, segsum, rid, run_start,
+                                                                     run_end, num_runs, drun);
   BK_STAMP(d, 5);
 }
 
@@ -2947,6 +2998,11 @@ __global__ __launch_bounds__(BkBig::THREADS) void k_bucket_big(
 #endif
 constexpr uint32_t RC_CHUNK = RL_RC_CHUNK;
 
+// unique_body's threshold between its two orders (k_run_check's cue to the host uses it too)
+#ifndef RL_UNIQ_DENSE
+#define RL_UNIQ_DENSE 3  // (A/B builds: quarters of the batch below which the list is walked; 5 = always, 0 = never)
+#endif
+
 template <typename Pred>
 __device__ __attribute__((always_inline)) inline uint32_t block_compact(uint32_t lo, uint32_t hi, uint32_t* list,
                                                                         uint32_t* count, Pred pred) {
@@ -2991,7 +3047,8 @@ __global__ __launch_bounds__(256) void k_run_check(BatchDev b, SRec rec_s,
                                                    const unsigned long long* num_runs, unsigned long long* split,
                                                    const uint32_t* sorted_n, uint32_t* __restrict__ pos_unit,
                                                    uint32_t* __restrict__ pos_hits, uint2* __restrict__ uniq,
-                                                   uint32_t* uniq_n, uint32_t* long_runs, uint32_t* __restrict__ keys0) {
+                                                   uint32_t* uniq_n, uint32_t* long_runs, uint32_t* __restrict__ keys0,
+                                                   int list_on, uint32_t* list_hint) {
   __shared__ uint32_t s_list[RC_CHUNK], s_cnt;
   if (blockIdx.x == 0 && threadIdx.x == 0) {  // k_split's reservations start from the bucket kernels' count
     split[0] = 0;
@@ -3000,9 +3057,15 @@ __global__ __launch_bounds__(256) void k_run_check(BatchDev b, SRec rec_s,
   }
   if (*err) return;
   const uint32_t sn = *sorted_n;
+  // The host's cue to have the keys-seen-once list built for the next batches:
+  // a sparse batch by unique_body's own test, with the descriptors outside the
+  // sorted order standing for the keys seen once (a large bucket's runs of
+  // one are missing from that count: it can only raise the cue sooner).
+  if (list_hint && blockIdx.x == 0 && threadIdx.x == 0 && (uint64_t)(b.n - min(sn, b.n)) * 4 < (uint64_t)b.n * RL_UNIQ_DENSE)
+    *list_hint = 1u;
   // a run of one (a large bucket sorts every element, light keys included) is
   // a key seen once: onto the list of k_table's singleton part
-  for (uint32_t q0 = blockIdx.x * RC_CHUNK; q0 < min(blockIdx.x * RC_CHUNK + RC_CHUNK, sn); q0 += blockDim.x) {
+  for (uint32_t q0 = blockIdx.x * RC_CHUNK; list_on && q0 < min(blockIdx.x * RC_CHUNK + RC_CHUNK, sn); q0 += blockDim.x) {
     const uint32_t q = q0 + threadIdx.x;
     const uint32_t k = q < sn ? skeys[q] : 0u;
     const bool one = q < sn && (q == 0 || skeys[q - 1] != k) && (q + 1 >= sn || skeys[q + 1] != k);
@@ -3037,9 +3100,11 @@ __global__ __launch_bounds__(256) void k_run_check(BatchDev b, SRec rec_s,
       // a dup mark (k_table's singleton part answers both) and the run is
       // emptied (its sorted path skips it); no k_split pass.
       run_end[r] = p;
-      const uint32_t at = atomicAdd(uniq_n, 2u);
-      uniq[at] = make_uint2(ep, skeys[q]);
-      uniq[at + 1] = make_uint2(eq, skeys[q]);
+      if (list_on) {
+        const uint32_t at = atomicAdd(uniq_n, 2u);
+        uniq[at] = make_uint2(ep, skeys[q]);
+        uniq[at + 1] = make_uint2(eq, skeys[q]);
+      }
       continue;
     }
     keys0[eq] = KEY_DUP;  // (the arrival-order key, not the record: KEY_DUP)
@@ -3228,7 +3293,7 @@ constexpr uint32_t SPLIT_THREADS = RL_SPLIT_THREADS;
 // The keys-seen-once list (Scratch::uniq) as k_split appends to it: a lone
 // one-element group is a key seen once (rare: one atomic each).
 struct UniqList {
-  uint2* list;
+  uint2* list;  // null: this batch builds no list (k_table answers its keys seen once in arrival order)
   uint32_t* n;
   const uint32_t* skeys;  // sorted keys: a run shares its sort key
   uint32_t* keys0;        // arrival-order keys (KEY_DUP marks)
@@ -3237,7 +3302,7 @@ struct UniqList {
   __device__ inline void single(uint32_t e, uint32_t p) const {
     const uint32_t k = skeys[p];
     keys0[e] = k;
-    list[atomicAdd(n, 1u)] = make_uint2(e, k);
+    if (list) list[atomicAdd(n, 1u)] = make_uint2(e, k);
   }
 };
 
@@ -3920,9 +3985,6 @@ __global__ __launch_bounds__(SPLIT_THREADS, RL_SPLIT_OCC) void k_split(BatchDev 
 //    probes (a workgroup's probes inside 1/1024 of the table): 5.35 vs 5.99 G
 //    with the list for every batch; tools/orderprobe.hip prices the whole
 //    access pattern per order and layout (profiles/r05/orderprobe.txt).
-#ifndef RL_UNIQ_DENSE
-#define RL_UNIQ_DENSE 3  // (A/B builds: quarters of the batch below which the list is walked; 5 = always, 0 = never)
-#endif
 __device__ __attribute__((always_inline)) inline void unique_body(uint32_t blk, BatchDev b, TableDev t, Params P, const Rec* __restrict__ rec,
                                                 const uint32_t* __restrict__ keys0,
                                                 const uint2* __restrict__ uniq, const uint32_t* uniq_n,
@@ -3931,13 +3993,15 @@ __device__ __attribute__((always_inline)) inline void unique_body(uint32_t blk, 
                                                 unsigned long long* stats, unsigned long long* stripes, uint32_t* err,
                                                 uint32_t* errs, int restore, const uint32_t* errb_prev) {
   __shared__ uint32_t s_err, s_nu, s_cnt, s_list[256];
+  const bool list_on = uniq_n != nullptr;  // (uniform; null: no list was built for this batch)
   if (threadIdx.x == 0) {
     s_err = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) | (errb_prev ? *errb_prev : 0u);
-    s_nu = *uniq_n;
+    s_nu = list_on ? *uniq_n : 0u;
   }
   __syncthreads();
   const uint32_t nu = s_nu;
-  const bool by_list = (uint64_t)nu * 4 < (uint64_t)b.n * RL_UNIQ_DENSE;  // (uniform) fewer than 75% keys seen once
+  // (uniform) a list, and fewer than 75% keys seen once
+  const bool by_list = list_on && (uint64_t)nu * 4 < (uint64_t)b.n * RL_UNIQ_DENSE;
   const uint32_t lo = blk * 256, hi = min(lo + 256, by_list ? nu : b.n);
   if (s_err || lo >= hi) return;
   refine_totals(b);
@@ -5596,7 +5660,8 @@ static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b -
 // validation word s.err. Sorted keys go to keys[1] (keys[0] keeps the arrival
 // order for k_table's keys seen once), the sort permutation to vals[0].
 void launch_stage_a(const BatchDev& b, const Scratch& s, int isolate, int per_second, hipStream_t st,
-                    hipEvent_t* ev, uint32_t* long_hint, bool long_kernel, uint32_t* big_hint, bool big_full) {
+                    hipEvent_t* ev, uint32_t* long_hint, bool long_kernel, uint32_t* big_hint, bool big_full,
+                    uint32_t* list_hint, bool list_on) {
   const uint32_t g0 = cdiv(b.n > b.n_req ? b.n : b.n_req, 256);
   if (ev) (void)hipEventRecord(ev[0], st);
   if (g0)
@@ -5609,11 +5674,9 @@ void launch_stage_a(const BatchDev& b, const Scratch& s, int isolate, int per_se
   if (ev) (void)hipEventRecord(ev[2], st);
   if (b.n) {
     const size_t seg_lds = (2ull * ptiles + 1) * 4;
-    k_bucket<<<PART_DIGITS, BkSmall::THREADS, seg_lds, st>>>(s.tile, s.part_info, ptiles,
-                                                             s.keys[1], s.vals[0], s.hits_s, s.segsum, s.rid,
-                                                             s.run_start, s.run_end, s.runs64, s.drun, s.big_meta, s.big_n,
-                                                             s.big_work, s.work_n, s.sorted_n, s.uniq, s.uniq_n,
-                                                             s.err, big_hint);
+    (list_on ? k_bucket<true> : k_bucket<false>)<<<PART_DIGITS, BkSmall::THREADS, seg_lds, st>>>(
+        s.tile, s.part_info, ptiles, s.keys[1], s.vals[0], s.hits_s, s.segsum, s.rid, s.run_start, s.run_end,
+        s.runs64, s.drun, s.big_meta, s.big_n, s.big_work, s.work_n, s.sorted_n, s.uniq, s.uniq_n, s.err, big_hint);
 #ifndef RL_EXP_NO_BIG  // (measurement builds only: without the large-bucket kernels, C1 has none)
     const uint32_t gi = big_full ? BIG_ITEM_BLOCKS : 1u, gb = big_full ? BIG_BLOCKS : 1u;
     k_big_count<<<gi, BkSmall::THREADS, seg_lds, st>>>(s.tile, s.part_info, ptiles,
@@ -5629,12 +5692,13 @@ void launch_stage_a(const BatchDev& b, const Scratch& s, int isolate, int per_se
 #endif
     k_run_check<<<cdiv(b.n, RC_CHUNK), 256, 0, st>>>(b, SRec{s.rec, s.vals[0]}, s.keys[1], s.rid, s.run_start,
                                                 s.run_end, s.run_flags, s.defer, s.defer_n, s.err, s.runs64, s.split,
-                                                s.sorted_n, s.grp, s.hit_t, s.uniq, s.uniq_n, s.long_runs, s.keys[0]);
+                                                s.sorted_n, s.grp, s.hit_t, s.uniq, s.uniq_n, s.long_runs, s.keys[0],
+                                                list_on ? 1 : 0, list_hint);
 #ifndef RL_EXP_NO_SPLIT  // (measurement builds only: C1 defers no run to k_split)
     k_split<<<SPLIT_BLOCKS, SPLIT_THREADS, 0, st>>>(b, SRec{s.rec, s.vals[0]}, s.vals[0], s.segsum, s.rid, s.run_start,
                                           s.run_end, s.run_flags, s.defer, s.defer_n, s.runs64, s.split, s.drun,
                                           b.n / 2 + BIG_HEAVY * PART_DIGITS, s.grp, s.lead, s.hit_t, s.vals[1], s.err,
-                                          per_second, UniqList{s.uniq, s.uniq_n, s.keys[1], s.keys[0]}, s.long_runs, long_hint,
+                                          per_second, UniqList{list_on ? s.uniq : nullptr, s.uniq_n, s.keys[1], s.keys[0]}, s.long_runs, long_hint,
                                           long_kernel ? 1 : 0);
 #endif
 #if RL_SPLIT_LONG_THREADS
@@ -5642,7 +5706,7 @@ void launch_stage_a(const BatchDev& b, const Scratch& s, int isolate, int per_se
       k_split_long<<<RL_SPLIT_LONG_BLOCKS, RL_SPLIT_LONG_THREADS, 0, st>>>(
           b, SRec{s.rec, s.vals[0]}, s.vals[0], s.segsum, s.rid, s.run_start, s.run_end, s.run_flags, s.defer,
           s.runs64, s.split, s.drun, b.n / 2 + BIG_HEAVY * PART_DIGITS, s.grp, s.lead, s.hit_t, s.vals[1], s.err,
-          per_second, UniqList{s.uniq, s.uniq_n, s.keys[1], s.keys[0]}, s.long_runs);
+          per_second, UniqList{list_on ? s.uniq : nullptr, s.uniq_n, s.keys[1], s.keys[0]}, s.long_runs);
 #endif
   }
 }
@@ -5669,7 +5733,7 @@ void launch_b_begin_early(const BatchDev& b, const OutDev& o, const Scratch& s, 
 
 void launch_stage_b(const BatchDev& b, const OutDev& o, const TableDev& t, const Params& P, const Scratch& s,
                     int restore, hipStream_t st, hipEvent_t* ev, const uint32_t* errb_prev, hipEvent_t table_done,
-                    unsigned long long* kt_acc, bool early, uint32_t* late_hint, bool late_full) {
+                    unsigned long long* kt_acc, bool early, uint32_t* late_hint, bool late_full, bool list_on) {
   const uint32_t m = restore ? 0u : b.n_rules * RL_NUM_STATS;
   const uint32_t gb = m ? (cdiv(m, 256) < 64 ? cdiv(m, 256) : 64) : 1;
   if (!early)
@@ -5691,7 +5755,7 @@ void launch_stage_b(const BatchDev& b, const OutDev& o, const TableDev& t, const
                                          s.run_flags, s.run_state, s.run_alias, s.rid, s.run_f, s.runs64, s.drun,
                                          s.defer2, s.defer2_n,
                                          s.keys[0], s.defer1, s.defer1_n, o.stats, s.stripes, s.errb, s.errs, restore,
-                                         s.fast_blk, s.uniq, s.uniq_n, kt_acc ? s.kt_blk : nullptr,
+                                         s.fast_blk, s.uniq, list_on ? s.uniq_n : nullptr, kt_acc ? s.kt_blk : nullptr,
                                          early ? errb_prev : nullptr);
     if (ev) (void)hipEventRecord(ev[4], st);
     if (!restore && P.lc_en)
