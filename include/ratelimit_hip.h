@@ -1052,6 +1052,65 @@ typedef struct rl_key_state {     /* host memory, same order */
 } rl_key_state;
 int rl_lookup(rl_ctx* ctx, const rl_keys* in, rl_key_state* out);
 
+/* ---- The busiest and the currently blocked keys (redis-cli --hotkeys, SCAN) --
+ * rl_hot_keys answers "which keys have the largest counters in the window the
+ * clock `now` falls in" and, with RL_HOT_BLOCKED, "which keys is the local
+ * over-limit cache rejecting at `now`", without moving the table to the host:
+ * one scan of the slots on the device, a selection there, k records back.
+ *
+ * It is defined against the export. A record matches when it is the record
+ * rl_export_range emits last for its key (the key's newest window) and
+ *   its unit is in unit_mask (0: every unit),
+ *   ws == now - now % div(unit),
+ *   now <= expire,
+ *   count >= min_count, and
+ *   with RL_HOT_BLOCKED, now < lc.
+ * A key whose window at `now` is no longer its newest (the clock ran back:
+ * that window lives in the history log) is NOT reported; the scan never walks
+ * the log.
+ *
+ * min(k, matched) records come back in `out` (the export's rl_records: n and
+ * stem_cap are the capacities on entry, n the records written on return,
+ * stem_off[n] the stem bytes written; flags are 0): every matching record
+ * with count > info->threshold, and for the rest records with count ==
+ * threshold (which of the tied ones is unspecified). Order: count descending,
+ * ties by stem bytes ascending (memcmp, the shorter first), then by unit.
+ * info->above counts the returned records above the threshold (0 when none
+ * is returned). k == 0: only *info (out may be NULL).
+ *
+ * A failed call writes nothing to `out`. RL_E_INVALID: a null q or info,
+ * unknown flags, a unit_mask bit outside 1..4, RL_HOT_BLOCKED on a ctx without
+ * local cache, out == NULL (or a null array in it) with k > 0, a ctx that
+ * joined a communicator. RL_E_CAPACITY: k > max_batch; or out->n / stem_cap
+ * (or the 32-bit stem offsets) too small for the result: *info is then filled
+ * (min(k, matched) records are needed, of at most 65535 stem bytes each).
+ * RL_E_TIME: now outside [0, 2^32 - 172801] or below the sweep floor.
+ *
+ * Orders after every submitted batch, is synchronous (it holds the batch
+ * pipeline for its duration, like the export) and strictly read-only, like
+ * rl_lookup: no slot, arena, flag, log entry, rl_table_info field or gauge
+ * moves. On a multi-shard ctx every shard selects its own top k on its own
+ * device and the host merges them; slots, matched and hits are summed,
+ * threshold and above describe the merged answer. */
+#define RL_HOT_BLOCKED 0x1u   /* only keys whose local over-limit cache entry is live: now < lc */
+typedef struct rl_hot_query {
+  int64_t  now;        /* the clock the table is read at */
+  uint32_t k;          /* records wanted, 0..max_batch; 0: only *info */
+  uint32_t min_count;  /* count >= min_count */
+  uint32_t unit_mask;  /* bit u (1..4) selects rl_unit u; 0 = every unit */
+  uint32_t flags;      /* RL_HOT_* */
+} rl_hot_query;
+typedef struct rl_hot_info {
+  uint64_t slots;      /* slots scanned (summed over shards) */
+  uint64_t matched;    /* records that satisfy the query */
+  uint64_t hits;       /* sum of their counts */
+  uint64_t above;      /* of them, with count > threshold */
+  uint32_t threshold;  /* count of the last record returned (0: none returned) */
+  uint32_t reserved;
+  int64_t  time_floor; /* the ctx's sweep floor */
+} rl_hot_info;
+int rl_hot_keys(rl_ctx* ctx, const rl_hot_query* q, rl_records* out, rl_hot_info* info);
+
 /* Per-stage device timing (HIP events on the batch stream), for benchmarks.
  * rl_profile(ctx, k) with k >= 1 starts accumulating over every k-th batch,
  * the first sampled one being the k-th submitted after the call (1 = every

@@ -24,7 +24,7 @@ EXPORTS = ["rl_abi_version", "rl_create", "rl_destroy", "rl_last_error", "rl_do_
            "rl_debug_log_tear", "rl_export_range", "rl_import", "rl_lookup", "rl_do_limit_requests_verdict",
            "rl_debug_verdict", "rl_request_batch_pack", "rl_do_limit_requests_packed_async",
            "rl_do_limit_wire_async", "rl_response_bound", "rl_do_limit_wire_respond_async", "rl_response_serialize",
-           "rl_debug_respond"]
+           "rl_debug_respond", "rl_hot_keys"]
 
 _libs = {}
 
@@ -120,6 +120,9 @@ def load(path):
         L.rl_import.argtypes = [C.c_void_p, C.POINTER(abi.RlRecords)]
     if hasattr(L, "rl_lookup"):
         L.rl_lookup.argtypes = [C.c_void_p, C.POINTER(abi.RlKeys), C.POINTER(abi.RlKeyState)]
+    if hasattr(L, "rl_hot_keys"):
+        L.rl_hot_keys.argtypes = [C.c_void_p, C.POINTER(abi.RlHotQuery), C.POINTER(abi.RlRecords),
+                                  C.POINTER(abi.RlHotInfo)]
     if hasattr(L, "rl_do_limit_requests_verdict"):
         L.rl_do_limit_requests_verdict.argtypes = [C.c_void_p, C.POINTER(abi.RlRequestBatch),
                                                    C.POINTER(abi.RlRequestResult), C.c_uint32,

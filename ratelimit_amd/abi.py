@@ -236,6 +236,20 @@ class RlKeyState(C.Structure):
 # the per-key arrays of rl_key_state
 KEY_STATE_DTYPES = {"status": np.uint8, "found": np.uint8, "count": np.uint32, "expire": np.uint32, "lc": np.uint32}
 
+RL_HOT_BLOCKED = 1  # rl_hot_query.flags: only keys whose local over-limit cache entry is live (now < lc)
+
+
+class RlHotQuery(C.Structure):
+    """rl_hot_query: what rl_hot_keys selects (the table read at `now`)."""
+    _fields_ = [("now", C.c_int64), ("k", C.c_uint32), ("min_count", C.c_uint32), ("unit_mask", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class RlHotInfo(C.Structure):
+    """rl_hot_info: totals of the records that satisfy an rl_hot_query."""
+    _fields_ = [("slots", C.c_uint64), ("matched", C.c_uint64), ("hits", C.c_uint64), ("above", C.c_uint64),
+                ("threshold", C.c_uint32), ("reserved", C.c_uint32), ("time_floor", C.c_int64)]
+
 RL_MATCH_NONE, RL_MATCH_UNLIMITED, RL_MATCH_LIMIT = 0, 1, 2
 REQUEST_ARRAYS = ("domain_bytes", "domain_off", "now", "hits", "req_idx", "entry_first", "desc_off", "desc_bytes",
                   "key_len", "value_len", "override_flags", "override_rpu", "override_unit", "override_rule")

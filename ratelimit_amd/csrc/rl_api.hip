@@ -878,6 +878,62 @@ int rl_lookup(rl_ctx* c, const rl_keys* in, rl_key_state* out) {
   return RL_OK;
 }
 
+int rl_hot_keys(rl_ctx* c, const rl_hot_query* q, rl_records* out, rl_hot_info* info) {
+  // (a single-shard ctx reports through its engine: rl_last_error reads it there)
+  auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };
+  if (!c || !q || !info) return bad(RL_E_INVALID, "gpu: null argument");
+  if (c->comm) return bad(RL_E_INVALID, "gpu: rl_hot_keys is not for a ctx that joined a communicator");
+  // the whole call is checked first: a failed call writes nothing
+  if (q->k && (!out || !out->stem_off || !out->unit || !out->flags || !out->ws || !out->count || !out->expire ||
+               !out->lc || (out->stem_cap && !out->stem_bytes)))
+    return bad(RL_E_INVALID, "gpu: rl_hot_keys: null rl_records (or one of its arrays) with k > 0");
+  for (uint32_t j = 0; j < c->n; j++)
+    if (const int rc = from_engine(c, c->e[j], eng_hot_check(c->e[j], q))) return rc;
+  if (const int src = settle_local(c)) return src;
+  // every shard's own top k on its own device, merged on the host: the top k
+  // of the union is the top k
+  std::vector<HotAnswer> ans(c->n);
+  std::vector<std::vector<rlhot::Rec>> part(c->n);
+  rl_hot_info sum{};
+  for (uint32_t j = 0; j < c->n; j++) {
+    rl_hot_info x{};
+    if (const int rc = from_engine(c, c->e[j], eng_hot_keys(c->e[j], q, &ans[j], &x))) return rc;
+    sum.slots += x.slots;
+    sum.matched += x.matched;
+    sum.hits += x.hits;
+    sum.time_floor = j ? std::max(sum.time_floor, x.time_floor) : x.time_floor;
+    const HotAnswer& a = ans[j];
+    for (size_t i = 0; i < a.count.size(); i++)
+      part[j].push_back(rlhot::Rec{a.count[i], a.ws[i], a.expire[i], a.lc[i], a.unit[i], a.len[i], a.stem.data() + a.off[i]});
+  }
+  const std::vector<rlhot::Rec> top = rlhot::merge(part, q->k);
+  rlhot::summarize(top, &sum.threshold, &sum.above);
+  uint64_t nb = 0;
+  for (const rlhot::Rec& r : top) nb += r.len;
+  *info = sum;
+  if (!out) return RL_OK;
+  if (top.size() > out->n || nb > out->stem_cap || nb > 0xFFFFFFFFull)
+    return bad(RL_E_CAPACITY, ("gpu: rl_hot_keys: the answer holds " + std::to_string(top.size()) + " records / " +
+                               std::to_string(nb) + " stem bytes: larger than rl_records")
+                                  .c_str());
+  out->n = (uint32_t)top.size();
+  if (out->stem_off) out->stem_off[0] = 0;
+  uint32_t at = 0;
+  for (size_t i = 0; i < top.size(); i++) {
+    const rlhot::Rec& r = top[i];
+    memcpy(out->stem_bytes + at, r.stem, r.len);
+    at += r.len;
+    out->stem_off[i + 1] = at;
+    out->unit[i] = (uint8_t)r.unit;
+    out->flags[i] = 0;
+    out->ws[i] = r.ws;
+    out->count[i] = r.count;
+    out->expire[i] = r.expire;
+    out->lc[i] = r.lc;
+  }
+  return RL_OK;
+}
+
 int rl_config_load(rl_ctx* c, const rl_config_tree* t) {
   if (!c) return fail(c, RL_E_INVALID, "gpu: null ctx");
   if (c->n > 1 && t && t->nodes)  // (the shards' own check allows their n x max_rules rows)

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/ratelimit_hip.h"
 #include "rl_device.h"
@@ -135,6 +136,7 @@ struct Engine {
   uint8_t* arena = nullptr;
   uint8_t* arena2 = nullptr;  // compaction target (rl_sweep), swapped with arena
   uint64_t arena_cap16 = 0;
+  uint64_t hot_range = 1ull << 22;  // slots per scan range of eng_hot_keys (RL_HOT_RANGE: tests cross ranges on tiny tables)
   // scratch: s[k] per buffer; stripes, counters, time floor, routing and the
   // table-stage error word are shared
   Scratch s[NBUF]{};
@@ -319,6 +321,17 @@ int eng_import(Engine* c, const rl_records* in);
 // reuses the staging of the host-buffer entry points: nothing is allocated.
 int eng_lookup_check(Engine* c, const rl_keys* in, const rl_key_state* out);
 int eng_lookup(Engine* c, const rl_keys* in, rl_key_state* out);
+// rl_hot_keys' checks of the query against this engine's limits (host only;
+// eng_hot_keys runs them too), and the scan of this engine's table: its top
+// q->k matching records in any order (record i's stem: stem[off[i]] .. + len[i])
+// and info's slots / matched / hits / time_floor; threshold and above are the
+// merge's (rl_api.hip). The call owns its device scratch and frees it.
+struct HotAnswer {
+  std::vector<uint8_t> stem, unit;
+  std::vector<uint32_t> off, len, ws, count, expire, lc;
+};
+int eng_hot_check(Engine* c, const rl_hot_query* q);
+int eng_hot_keys(Engine* c, const rl_hot_query* q, HotAnswer* ans, rl_hot_info* info);
 
 // Owner side of a routed batch, pipelined on the engine's streams like
 // eng_do_limit_async: unpack the n received wire records (chunks of n_src

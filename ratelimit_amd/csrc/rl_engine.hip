@@ -533,6 +533,8 @@ Engine* eng_create(const rl_config* cfg_in, char* err, size_t errlen) {
   ok = ok && hipHostMalloc((void**)&c->h_list, NBUF * sizeof(uint32_t)) == hipSuccess;
   if (ok) memset(c->h_list, 0, NBUF * sizeof(uint32_t));
   if (const char* uc = getenv("RL_LIST_CUE")) c->list_mode = atoi(uc);  // (A/B knob)
+  if (const char* hr = getenv("RL_HOT_RANGE"))  // (eng_hot_keys' scan range in slots, 64 .. 2^22)
+    c->hot_range = std::min<uint64_t>(std::max<uint64_t>(strtoull(hr, nullptr, 0), 64), 1ull << 22);
   if (!ok) return fail("gpu: device allocation failed (table_slots/arena/max_batch too large?)", c);
   ok = hipMemsetAsync(c->slots, 0, c->nslots * sizeof(Slot), c->stream) == hipSuccess &&
        hipMemsetAsync(c->log_ctr, 0, (size_t)(LOG_PARTS + 1) * LOG_CTR_STRIDE * 8, c->stream) == hipSuccess &&
@@ -2810,6 +2812,95 @@ int eng_export_range(Engine* c, uint64_t s0, uint64_t s1, rl_records* out, rl_ex
   HIPCHK(c, hipStreamSynchronize(st));
   out->stem_off[nrec] = (uint32_t)nb;
   if (h_tot[4] != ((nrec << 32) | nb)) return set_err(c, RL_E_INTERNAL, "gpu: export wrote other than it counted");
+  return RL_OK;
+}
+
+int eng_hot_check(Engine* c, const rl_hot_query* q) {
+  if (!c || !q) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (q->flags & ~RL_HOT_BLOCKED) return set_err(c, RL_E_INVALID, "gpu: rl_hot_keys: unknown flags");
+  if (q->unit_mask & ~rlhot::UNIT_BITS) return set_err(c, RL_E_INVALID, "gpu: rl_hot_keys: unit_mask bit outside 1..4");
+  if ((q->flags & RL_HOT_BLOCKED) && !c->cfg.local_cache_enabled)
+    return set_err(c, RL_E_INVALID, "gpu: rl_hot_keys: RL_HOT_BLOCKED on a ctx without local cache");
+  if (q->k > c->cfg.max_batch) return set_err(c, RL_E_CAPACITY, "gpu: rl_hot_keys: k exceeds configured max_batch");
+  if (q->now < 0 || q->now > (int64_t)NOW_MAX) return set_err(c, RL_E_TIME, "gpu: now out of range");
+  return RL_OK;
+}
+
+int eng_hot_keys(Engine* c, const rl_hot_query* q, HotAnswer* ans, rl_hot_info* info) {
+  if (!c || !q || !ans || !info) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (const int rc = eng_hot_check(c, q)) return rc;
+  RQ_SETTLE(c);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream;
+  HIPCHK(c, after_batches(c, st));
+  int64_t floor = 0;
+  HIPCHK(c, hipMemcpyAsync(&floor, c->s[0].time_floor, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (q->now < floor) return set_err(c, RL_E_TIME, "gpu: now below the sweep floor");
+  const uint32_t k = q->k;
+  const uint64_t range = std::min<uint64_t>(c->hot_range, c->nslots);
+  const uint64_t pool_cap = k ? range + 2ull * k : 0;  // (< 2^32: range <= 2^22, k <= max_batch <= 2^23)
+  const rlhot::Query dq{(uint32_t)q->now, q->min_count, q->unit_mask, q->flags};
+  DevBufs mem;
+  HotState* hs = nullptr;
+  unsigned long long* pool = nullptr;
+  HIPCHK(c, mem.get(&hs, 1));
+  if (k) HIPCHK(c, mem.get(&pool, pool_cap));
+  HIPCHK(c, hipMemsetAsync(hs, 0, sizeof(HotState), st));
+  const TableDev t = table_view(c);
+  // The ranges start small and double up to `range`: the first cut then runs
+  // on a pool of a few K entries, not on every match of 2^22 slots (one
+  // workgroup selects), and with its threshold the later ranges add little.
+  for (uint64_t s0 = 0, r = std::min<uint64_t>(range, 4096); s0 < c->nslots; r = std::min(2 * r, range)) {
+    const uint64_t s1 = std::min(s0 + r, c->nslots);
+    launch_hot_scan(t, s0, s1, dq, k, hs, pool, (uint32_t)pool_cap, st);
+    if (k) launch_hot_select(hs, pool, (uint32_t)pool_cap, k, 2 * k, st);
+    s0 = s1;
+  }
+  if (k) {
+    launch_hot_select(hs, pool, (uint32_t)pool_cap, k, k, st);
+    launch_hot_size(t, hs, pool, (uint32_t)pool_cap, k, st);
+  }
+  HIPCHK(c, hipGetLastError());
+  HotState h{};
+  HIPCHK(c, hipMemcpyAsync(&h, hs, sizeof h, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (h.err || h.pool_n > k) return set_err(c, RL_E_INTERNAL, "gpu: rl_hot_keys: the candidate pool overflowed");
+  *info = rl_hot_info{};
+  info->slots = c->nslots;
+  info->matched = h.matched;
+  info->hits = h.hits;
+  info->time_floor = floor;
+  const uint32_t n = h.pool_n;
+  const uint64_t nb = h.stem_bytes;
+  *ans = HotAnswer{};
+  if (!n) return RL_OK;
+  HotOutDev o{};
+  o.stem_cap = nb;
+  HIPCHK(c, mem.get(&o.stem, nb));
+  HIPCHK(c, mem.get(&o.off, n));
+  HIPCHK(c, mem.get(&o.len, n));
+  HIPCHK(c, mem.get(&o.unit, n));
+  HIPCHK(c, mem.get(&o.ws, n));
+  HIPCHK(c, mem.get(&o.count, n));
+  HIPCHK(c, mem.get(&o.expire, n));
+  HIPCHK(c, mem.get(&o.lc, n));
+  launch_hot_gather(t, hs, pool, n, o, st);
+  HIPCHK(c, hipGetLastError());
+  ans->stem.resize(nb);
+  ans->unit.resize(n);
+  for (std::vector<uint32_t>* v : {&ans->off, &ans->len, &ans->ws, &ans->count, &ans->expire, &ans->lc}) v->resize(n);
+  HIPCHK(c, hipMemcpyAsync(ans->stem.data(), o.stem, nb, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(ans->off.data(), o.off, n * 4ull, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(ans->len.data(), o.len, n * 4ull, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(ans->unit.data(), o.unit, n, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(ans->ws.data(), o.ws, n * 4ull, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(ans->count.data(), o.count, n * 4ull, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(ans->expire.data(), o.expire, n * 4ull, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(ans->lc.data(), o.lc, n * 4ull, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(&h, hs, sizeof h, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (h.err || h.cursor != nb) return set_err(c, RL_E_INTERNAL, "gpu: rl_hot_keys gathered other than it sized");
   return RL_OK;
 }
 

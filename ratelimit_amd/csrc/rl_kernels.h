@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "rl_device.h"
+#include "rl_hot_select.h"
 
 namespace rl {
 
@@ -435,6 +436,40 @@ struct LookupDev {
 // key and nothing else: no slot, no arena space, no log entry, no counter.
 void launch_lookup(const TableDev& t, const HashKey& hk, const Params& P, const int64_t* time_floor,
                    const uint8_t* stem, uint32_t stem_total, const LookupDev& q, hipStream_t st);
+// ---- the busiest / blocked keys (rl_hot_keys, rl_hot.hip): a read-only scan ----
+// One call's device state (zero at its start).
+struct HotState {
+  unsigned long long matched, hits;  // records that satisfy the query, the sum of their counts
+  unsigned long long stem_bytes;     // the winners' stems (k_hot_size)
+  unsigned long long cursor;         // stem bytes the gather has reserved
+  uint32_t pool_n;                   // entries in the candidate pool
+  uint32_t thr, full;                // full: the pool was cut to K entries, all with count >= thr
+  uint32_t err;                      // (internal checks: 1 the pool overflowed, 2 the gather's stems did)
+};
+// Device staging of the winners (any order; the host sorts): off / len = each
+// record's stem in `stem` (stem_cap bytes).
+struct HotOutDev {
+  uint8_t* stem;
+  uint64_t stem_cap;
+  uint32_t *off, *len;
+  uint8_t* unit;
+  uint32_t *ws, *count, *expire, *lc;
+};
+// The slots [s0, s1): st->matched / hits += the matching records, and count <<
+// 32 | slot of the candidates among them appended to pool (pool_cap entries:
+// at least 2k + s1 - s0). k = records wanted (0: no pool).
+void launch_hot_scan(const TableDev& t, uint64_t s0, uint64_t s1, const rlhot::Query& q, uint32_t k, HotState* st,
+                     unsigned long long* pool, uint32_t pool_cap, hipStream_t stream);
+// If the pool holds more than `limit` (>= k) entries: cut it to the k largest
+// counts and raise the scan's threshold to the smallest of them.
+void launch_hot_select(HotState* st, unsigned long long* pool, uint32_t pool_cap, uint32_t k, uint32_t limit,
+                       hipStream_t stream);
+// st->stem_bytes += the stems of the pool's entries (at most k), and the
+// gather of its first n entries into o.
+void launch_hot_size(const TableDev& t, HotState* st, const unsigned long long* pool, uint32_t pool_cap, uint32_t k,
+                     hipStream_t stream);
+void launch_hot_gather(const TableDev& t, HotState* st, const unsigned long long* pool, uint32_t n, const HotOutDev& o,
+                       hipStream_t stream);
 // Built with RL_LOG_TEAR (rl_debug_log_tear's hook in the history log's lookups)?
 bool log_tear_hook();
 void launch_debug_keys(const BatchDev& b, uint8_t* out, uint32_t* klen, hipStream_t st);

@@ -30,6 +30,7 @@
 
 #include "rl_device.h"
 #include "rl_kernels.h"
+#include "rl_slot_img.h"
 
 // Ablation switches for profiling builds only (RL_ABL bits; 0 in the product):
 // 1 = no table probe (slot = tag & mask), 2 = no replay body, 4 = no stats flush.
@@ -628,8 +629,6 @@ __device__ inline bool key_equal(const Key& x, const Key& y) {
 // ===========================================================================
 // HBM table probing.
 // ===========================================================================
-__device__ inline uint32_t u4w(const uint4& a, uint32_t j) { return j == 0 ? a.x : j == 1 ? a.y : j == 2 ? a.z : a.w; }
-
 // Stem dword k (static in unrolled loops): the zero-padded head, then the packed stems.
 __device__ inline uint32_t key_dw(const Key& key, uint32_t k) {
   return k < KEY_HEAD / 4 ? u4w(key.h[k >> 2], k & 3) : key.st.word(k);
@@ -644,8 +643,6 @@ __device__ inline uint32_t arena_diff(const uint8_t* arena, uint32_t ext_off, co
   if (rest & 3) d |= (ek[rw] ^ key.st.word(KEY_SPLIT / 4 + rw)) & tail_mask(rest);
   return d;
 }
-
-__device__ inline uint32_t slot_ext(const Slot* s) { return reinterpret_cast<const uint32_t*>(s)[SLOT_EXT_DW]; }
 
 // Slot stem == `key`? Only the stem's own dwords are read (the last one masked).
 __device__ inline bool slot_key_equal(const Slot* s, const Key& key, const uint8_t* arena) {
@@ -768,26 +765,7 @@ __device__ __attribute__((always_inline)) inline int64_t find_slot(const TableDe
   return SLOT_TABLE_FULL;
 }
 
-// A slot image for probing: the whole 64-B slot (tag, length, flags, cur,
-// history chain head, stem bytes 0..35). Plain loads are enough: within a launch only
-// CAS inserts change tags, and a lane only ever looks for its own stem, which
-// no other lane inserts.
-struct SlotImg {
-  uint4 v[4];
-  __device__ inline uint32_t dw(uint32_t k) const { return u4w(v[k >> 2], k & 3); }
-  __device__ inline uint32_t tag() const { return v[0].x; }
-  __device__ inline uint32_t key_len() const { return v[0].y & 0xFFFFu; }
-  __device__ inline uint32_t unit() const { return (v[0].y >> 16) & 0xFFu; }
-  __device__ inline uint32_t flags() const { return v[0].y >> 24; }
-  __device__ inline Win cur() const { return Win{v[0].z, v[0].w, v[1].x, v[1].y}; }
-  __device__ inline uint32_t ring() const { return v[1].z; }
-};
-
-__device__ inline void load_img_lo(const Slot* s, SlotImg& im) {
-  const uint4* p = reinterpret_cast<const uint4*>(s);
-#pragma unroll
-  for (int j = 0; j < 4; j++) im.v[j] = p[j];
-}
+// (SlotImg, the whole 64-B slot image a probe reads, and load_img_lo: rl_slot_img.h)
 
 // Stem of `key` == the slot's stem? A stem longer than KEY_IN compares its
 // tail with the arena.
@@ -1136,12 +1114,6 @@ struct LaneStats {
     for (int i = 0; i < RL_NUM_STATS; i++) v[i] += d[i];
   }
 };
-
-__device__ inline unsigned long long wave_sum(unsigned long long x) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-  return x;
-}
 
 // All lanes of the wave must call this (converged).
 __device__ __attribute__((always_inline)) inline void wave_flush(LaneStats& L, StatAcc& acc) {
@@ -5284,16 +5256,6 @@ __global__ __launch_bounds__(256) void k_export_count(const TableDev t, uint64_t
   if (threadIdx.x < 4) {
     const unsigned long long x = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
     if (x) atomicAdd(&tot[threadIdx.x], x);
-  }
-}
-
-// A slot's whole stem: its inline bytes, then (longer than KEY_IN) the arena's.
-__device__ inline void export_stem(const TableDev& t, const Slot* s, uint32_t len, uint8_t* dst) {
-  const uint32_t il = slot_inline(len);
-  for (uint32_t k = 0; k < il; k++) dst[k] = s->key[k];
-  if (len > KEY_IN) {
-    const uint8_t* ek = t.arena + (size_t)slot_ext(s) * 16;
-    for (uint32_t k = KEY_SPLIT; k < len; k++) dst[k] = ek[k - KEY_SPLIT];
   }
 }
 

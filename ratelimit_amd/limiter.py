@@ -30,7 +30,7 @@ from .types import OK, DescriptorStatus, Limit  # noqa: F401  (re-exported data 
 STAGES = ("prepare", "sort", "segment", "table", "finish")
 PROFILE_FIELDS = STAGES + ("table_kernel",)  # + k_table's own run time (device clock)
 
-__all__ = ["GpuRateLimitCache", "GpuRateLimitService", "KeyState", "RedisError", "RequestVerdict", "TimeSource",
+__all__ = ["GpuRateLimitCache", "GpuRateLimitService", "HotKey", "KeyState", "RedisError", "RequestVerdict", "TimeSource",
            "migrate"]
 
 
@@ -41,6 +41,18 @@ class KeyState(NamedTuple):
     count: int
     ttl_s: Optional[int]
     over_limit_cached: bool
+
+
+class HotKey(NamedTuple):
+    """One record of GpuRateLimitCache.hot_keys: the key's stem and unit, its
+    window's start, counter and expiry, and the expiry of its local over-limit
+    cache entry (0: none)."""
+    stem: bytes
+    unit: int
+    ws: int
+    count: int
+    expire: int
+    lc: int
 
 
 class TimeSource:
@@ -719,6 +731,45 @@ class Backend:
             lo = hi
         return out
 
+    # ---- the busiest / the currently blocked keys (redis-cli --hotkeys, SCAN with a filter)
+    def hot_keys(self, now: int, k: int, min_count: int = 0, units=None, blocked: bool = False):
+        """rl_hot_keys -> (records, info): the k matching records with the largest
+        counts in the windows `now` falls in (export_range's arrays; count
+        descending, ties by stem bytes, then unit) and rl_hot_info as a dict.
+        units: the rl_unit values to select (None: every unit); blocked: only
+        keys the local over-limit cache rejects at `now`. The buffers are sized
+        from k; on RL_E_CAPACITY (long stems) they grow to what info allows
+        (min(k, matched) records of at most 65535 stem bytes) and the call is
+        retried once."""
+        q = abi.RlHotQuery()
+        q.now, q.k, q.min_count = int(now), int(k), int(min_count)
+        q.unit_mask = 0
+        for u in (units if units is not None else ()):
+            q.unit_mask |= 1 << int(u)
+        q.flags = abi.RL_HOT_BLOCKED if blocked else 0
+        info = abi.RlHotInfo()
+        n_cap, stem_cap = int(k), max(1 << 16, 128 * int(k))
+        for attempt in (0, 1):
+            bufs = {"stem_bytes": np.empty(max(stem_cap, 1), np.uint8), "stem_off": np.zeros(n_cap + 1, np.uint32)}
+            for f, dt in abi.RECORD_DTYPES.items():
+                bufs[f] = np.zeros(max(n_cap, 1), dt)
+            r = abi.RlRecords()
+            r.n, r.stem_cap = n_cap, stem_cap
+            for f, v in bufs.items():
+                setattr(r, f, abi.ptr(v))
+            rc = self.L.rl_hot_keys(self.ctx, C.byref(q), C.byref(r), C.byref(info))
+            if rc == abi.RL_E_CAPACITY and attempt == 0:
+                n_cap = min(int(k), int(info.matched))
+                stem_cap = min(max(n_cap, 1) * 65535, (1 << 32) - 1)
+                continue
+            self._check(rc)
+            break
+        n = r.n
+        rec = {f: bufs[f][:n] for f in abi.RECORD_DTYPES}
+        rec["stem_off"] = bufs["stem_off"][:n + 1]
+        rec["stem_bytes"] = bufs["stem_bytes"][:int(bufs["stem_off"][n])]
+        return rec, {f: getattr(info, f) for f, _ in abi.RlHotInfo._fields_ if f != "reserved"}
+
     def debug_keys(self, pb: PackedBatch) -> List[str]:
         cap = int(pb.arrays["stem_off"][-1]) + 24 * pb.n + 1
         buf = np.zeros(cap, np.uint8)
@@ -881,6 +932,19 @@ class GpuRateLimitCache:
             out[i] = KeyState(int(res["count"][j]), int(res["expire"][j]) - now if found else None,
                               bool(res["lc"][j]))
         return out
+
+    def hot_keys(self, k: int, now: Optional[int] = None, min_count: int = 0, units=None,
+                 blocked: bool = False) -> list:
+        """The k keys with the largest counters in the windows `now` (default: the
+        time source's) falls in, busiest first; blocked=True: only the keys the
+        local over-limit cache is rejecting at `now`. Stems are the cache's own
+        (prefix ‖ domain ‖ entries); the Redis key is stem ‖ decimal(ws)."""
+        now = self.time_source.unix_now() if now is None else int(now)
+        rec, _ = self.backend.hot_keys(now, k, min_count, units, blocked)
+        off, blob = rec["stem_off"], rec["stem_bytes"]
+        return [HotKey(bytes(blob[int(off[i]):int(off[i + 1])]), int(rec["unit"][i]), int(rec["ws"][i]),
+                       int(rec["count"][i]), int(rec["expire"][i]), int(rec["lc"][i]))
+                for i in range(len(rec["ws"]))]
 
     def flush(self):
         """Flush(): nothing is asynchronous on the host path."""
