@@ -38,7 +38,8 @@ extern "C" {
 enum rl_status {
   RL_OK = 0,
   RL_E_INVALID = 1,    /* malformed batch: unit out of 1..4, offsets, sizes */
-  RL_E_TABLE_FULL = 2, /* open-addressing table has no free slot on the probe path */
+  RL_E_TABLE_FULL = 2, /* the key's probe window (min(table_slots, 65536) slots from its home)
+                          holds neither an empty slot nor a tombstone: raise table_slots */
   RL_E_ARENA_FULL = 3, /* long-stem overflow arena exhausted */
   RL_E_HIP = 4,        /* HIP runtime error */
   RL_E_CAPACITY = 5,   /* batch larger than rl_config.max_* */
@@ -353,7 +354,12 @@ int rl_do_limit_prefixed_async(rl_ctx* ctx, const rl_batch_prefixed* in, rl_resu
 
 /* Epoch sweep (replaces Redis EXPIRE): tombstones every slot whose counter
  * and local-cache entries have all expired at `now`; `now` becomes a floor
- * (later requests with an earlier time fail with RL_E_TIME). */
+ * (later requests with an earlier time fail with RL_E_TIME). Inserts reuse
+ * tombstones; when fewer than a quarter of the slots are empty after the
+ * eviction, the sweep also turns every tombstone that no live key's probe path
+ * crosses back into an empty slot (one more pass that rehashes the live stems),
+ * so a table under key turnover keeps short probes and rl_table_info.tombstones
+ * may fall from one sweep to the next. *n_evicted counts evicted keys only. */
 int rl_sweep(rl_ctx* ctx, int64_t now, uint64_t* n_evicted);
 
 /* Seed / restore counters (host buffers). */

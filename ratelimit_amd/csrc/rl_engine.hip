@@ -1321,6 +1321,10 @@ int eng_restore(Engine* c, const rl_restore_batch* r) {
   return rc;
 }
 
+// rl_sweep reclaims tombstones when fewer than 1 / SWEEP_RECLAIM_EMPTY_DIV of
+// the slots are empty after the eviction (the reasoning: eng_sweep).
+constexpr uint64_t SWEEP_RECLAIM_EMPTY_DIV = 4;
+
 int eng_sweep(Engine* c, int64_t now, uint64_t* n_evicted) {
   if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
   RQ_SETTLE(c);
@@ -1332,7 +1336,7 @@ int eng_sweep(Engine* c, int64_t now, uint64_t* n_evicted) {
   HIPCHK(c, hipMemcpyAsync(&last, c->s[0].time_floor, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (now > last) HIPCHK(c, hipMemcpyAsync(c->s[0].time_floor, &now, 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->s[0].counters, 0, 8, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->s[0].counters, 0, 16, c->stream));
   {
     const TableDev t = table_view(c);
     launch_sweep(t, c->nslots, (uint32_t)now, c->s[0].counters, c->stream);
@@ -1341,6 +1345,7 @@ int eng_sweep(Engine* c, int64_t now, uint64_t* n_evicted) {
   HIPCHK(c, hipMemcpyAsync(c->h_counters, c->s[0].counters, 40, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (n_evicted) *n_evicted = c->h_counters[0];
+  const uint64_t n_used = c->h_counters[1];  // live slots and tombstones after the eviction
   if (c->h_counters[0] && c->h_counters[4]) {
     // reclaim the long-stem arena: live slots' overflow bytes move to the spare
     // arena, packed from 0, and the two swap (counters[4] = the arena cursor)
@@ -1349,6 +1354,33 @@ int eng_sweep(Engine* c, int64_t now, uint64_t* n_evicted) {
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::swap(c->arena, c->arena2);
+  }
+  // Tombstone reclamation. Nothing else ever makes a slot empty again, and a
+  // miss (a lookup, and the probe before every insert) walks to the first
+  // empty slot, so a table that only loses empties ends with misses as long as
+  // the probe window and inserts that find no slot. The pass rehashes every
+  // live stem, so a table with empties to spare skips it: linear probing at a
+  // load of 3/4 (tombstones counted) still ends an average miss within about
+  // (1 + 1 / (1 - 3/4)^2) / 2 = 8.5 slots (Knuth), and that load is the
+  // customary point to rebuild an open-addressing table. Below a quarter
+  // empty, every sweep reclaims.
+  static const bool always = [] {
+    const char* e = getenv("RL_SWEEP_RECLAIM");  // (measurements: "1" reclaims on every sweep)
+    return e && e[0] == '1';
+  }();
+  if (always || (c->nslots - n_used) * SWEEP_RECLAIM_EMPTY_DIV < c->nslots) {
+    uint32_t* need = nullptr;  // one bit per slot, for this call only
+    const size_t words = (size_t)((c->nslots + 31) / 32);
+    HIPCHK(c, dalloc(&need, words));
+    hipError_t e = hipMemsetAsync(need, 0, words * 4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->s[0].counters, 0, 16, c->stream);
+    if (e == hipSuccess) {
+      launch_reclaim(table_view(c), c->hk, c->nslots, need, c->s[0].counters, c->stream);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(need);
+    HIPCHK(c, e);
   }
   return RL_OK;
 }

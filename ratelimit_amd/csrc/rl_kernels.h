@@ -380,10 +380,16 @@ void launch_route_ret(const unsigned long long* res, uint32_t n, const uint32_t*
 // out[i] = sum over blocks b of stage[b * stride + i], i < m (stride 0: m).
 void launch_stats_sum(const unsigned long long* stage, uint32_t n_blocks, uint32_t m, unsigned long long* out,
                       hipStream_t st, uint32_t stride = 0);
-// The epoch sweep: evict the slots whose records (cur and logged) are all dead.
+// The epoch sweep: evict the slots whose records (cur and logged) are all dead
+// (evicted[0]: how many; evicted[1]: the slots that are not empty afterwards).
 void launch_sweep(const TableDev& t, uint64_t nslots, uint32_t now, unsigned long long* evicted, hipStream_t st);
 void launch_arena_compact(Slot* slots, uint64_t nslots, const uint8_t* from, uint8_t* to, unsigned long long* used16,
                           hipStream_t st);
+// Tombstones that lie in no live key's [home, slot) become empty slots. need:
+// (nslots + 31) / 32 zeroed words; ctr[0] (zeroed) counts slots whose stem does
+// not hash to their tag (then nothing is freed), ctr[1] the tombstones freed.
+void launch_reclaim(const TableDev& t, const HashKey& hk, uint64_t nslots, uint32_t* need, unsigned long long* ctr,
+                    hipStream_t st);
 void launch_lc_count(const TableDev& t, uint64_t nslots, uint32_t now, unsigned long long* out, hipStream_t st);
 void launch_table_info(const Slot* slots, uint64_t nslots, unsigned long long* out, hipStream_t st);
 // ---- export / import of window records (rl_export_range, rl_import) ----

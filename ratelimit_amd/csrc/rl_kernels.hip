@@ -709,18 +709,45 @@ __device__ inline uint32_t slot_fail_status(int64_t r) {
 
 // Claim slot i (expected tag `from`) for (stem, unit) and initialise it.
 // 1: claimed, 0: lost the race, -1: the arena is full (the slot is a tombstone again).
-__device__ __attribute__((always_inline)) inline int slot_claim(const TableDev& t, uint64_t i, uint32_t from, uint32_t tag, const Key& key,
-                                 uint32_t unit) {
-  Slot* s = &t.slots[i];
-  if (atomicCAS(&s->tag, from, tag) != from) return 0;
+__device__ __attribute__((always_inline)) inline int slot_fill(const TableDev& t, uint64_t i, const Key& key, uint32_t unit) {
+  Slot* s = &t.slots[i];  // (its tag is this lane's already)
   if (slot_init(t, s, key, unit)) return 1;
   __hip_atomic_store(&s->tag, TAG_TOMB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return -1;
 }
+__device__ __attribute__((always_inline)) inline int slot_claim(const TableDev& t, uint64_t i, uint32_t from, uint32_t tag, const Key& key,
+                                 uint32_t unit) {
+  if (atomicCAS(&t.slots[i].tag, from, tag) != from) return 0;
+  return slot_fill(t, i, key, unit);
+}
+
+// The tag CAS of a tombstone claim, for a key known absent from the slots
+// [tomb, end) of its probe path (end == tomb: the whole table), `tomb` being the
+// first tombstone it met: that one, or, where another lane's CAS took it
+// first, the next tombstone before `end` (a lane that went on to a far empty
+// slot instead would pin every tombstone on the way there). Returns the slot
+// whose tag is now `tag` (the caller fills it: slot_fill), or -1. Not inlined,
+// and without the key: the probe loops of the batch kernels keep their
+// registers.
+__device__ __attribute__((noinline)) int64_t cas_tombstone(Slot* slots, uint64_t mask, uint64_t tomb, uint64_t end, uint32_t tag) {
+  uint64_t j = tomb;
+  for (uint64_t n = ((end - tomb - 1) & mask) + 1; n; n--, j = (j + 1) & mask) {
+    if (__hip_atomic_load(&slots[j].tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != TAG_TOMB) continue;
+    if (atomicCAS(&slots[j].tag, TAG_TOMB, tag) == TAG_TOMB) return (int64_t)j;
+  }
+  return -1;
+}
 
 // Find (and optionally insert) the slot of (stem, unit). Returns SLOT_ABSENT
-// when absent and insert == false, SLOT_TABLE_FULL / SLOT_ARENA_FULL (error
-// bit set in *err) when it cannot be inserted. Linear probing over 64-B slots
+// when absent and insert == false (a window that ends without an empty slot
+// included), SLOT_TABLE_FULL / SLOT_ARENA_FULL (error bit set in *err) when it
+// cannot be inserted: the table is full for a key only when its whole probe
+// window (max_probe slots from its home) holds neither an empty slot nor a
+// tombstone it could claim. An insert walks to the first empty slot or to the
+// window's end (the key may lie behind tombstones; the position past the
+// window stands for an empty slot that nobody can claim), then claims a
+// tombstone of the path it walked (cas_tombstone), else the empty slot.
+// Linear probing over 64-B slots
 // from the home slot = top bits of the stem hash, i.e. of the sort key:
 // consecutive runs probe increasing slots (page and TLB locality). A tag
 // match is confirmed by the full stem (collision-exact). Inserts claim the
@@ -731,9 +758,10 @@ __device__ __attribute__((always_inline)) inline int64_t find_slot(const TableDe
   uint64_t i = hstem >> t.shift;
   int64_t tomb = -1;
   *inserted = false;
-  for (uint32_t p = 0; p < t.max_probe; p++, i = (i + 1) & t.mask) {
+  for (uint32_t p = 0; p <= t.max_probe; p++, i = (i + 1) & t.mask) {
+    const bool end = p == t.max_probe;
     Slot* s = &t.slots[i];
-    const uint32_t st = __hip_atomic_load(&s->tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t st = end ? TAG_EMPTY : __hip_atomic_load(&s->tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (st == tag) {  // (a 32-bit tag is a filter: the unit and the stem bytes decide)
       if (s->unit == unit && slot_key_equal(s, key, t.arena)) return (int64_t)i;
       continue;
@@ -743,14 +771,15 @@ __device__ __attribute__((always_inline)) inline int64_t find_slot(const TableDe
       continue;
     }
     if (st != TAG_EMPTY) continue;
-    // (stem, unit) is absent: claim the first tombstone on the path, else this slot.
+    // (stem, unit) is absent: claim a tombstone on the path, the first one first, else this slot.
     if (!insert) return SLOT_ABSENT;
-    int c = tomb >= 0 ? slot_claim(t, (uint64_t)tomb, TAG_TOMB, tag, key, unit) : 0;
+    if (tomb >= 0) tomb = cas_tombstone(t.slots, t.mask, (uint64_t)tomb, i, tag);
+    int c = tomb >= 0 ? slot_fill(t, (uint64_t)tomb, key, unit) : 0;
     if (c > 0) {
       *inserted = true;
       return tomb;
     }
-    if (c == 0) c = slot_claim(t, i, TAG_EMPTY, tag, key, unit);
+    if (c == 0 && !end) c = slot_claim(t, i, TAG_EMPTY, tag, key, unit);
     if (c > 0) {
       *inserted = true;
       return (int64_t)i;
@@ -1037,9 +1066,10 @@ __device__ __attribute__((always_inline)) inline int64_t find_slot_img(const Tab
   uint64_t i = hstem >> t.shift;
   int64_t tomb = -1;
   *inserted = false;
-  for (uint32_t p = 0; p < t.max_probe; p++, i = (i + 1) & t.mask) {
-    if (p) load_img_lo(&t.slots[i], im);
-    const uint32_t st = im.tag();
+  for (uint32_t p = 0; p <= t.max_probe; p++, i = (i + 1) & t.mask) {
+    const bool end = p == t.max_probe;  // (past the window: an empty slot that nobody can claim)
+    if (p && !end) load_img_lo(&t.slots[i], im);
+    const uint32_t st = end ? TAG_EMPTY : im.tag();
     if (st == tag) {  // (a 32-bit tag is a filter: the unit and the stem bytes decide)
       if (im.unit() == unit && img_key_equal(im, key, t.arena)) return (int64_t)i;
       continue;
@@ -1050,9 +1080,10 @@ __device__ __attribute__((always_inline)) inline int64_t find_slot_img(const Tab
     }
     if (st != TAG_EMPTY) continue;
     int64_t at = -1;
-    int c = tomb >= 0 ? slot_claim(t, (uint64_t)tomb, TAG_TOMB, tag, key, unit) : 0;
+    if (tomb >= 0) tomb = cas_tombstone(t.slots, t.mask, (uint64_t)tomb, i, tag);
+    int c = tomb >= 0 ? slot_fill(t, (uint64_t)tomb, key, unit) : 0;
     if (c > 0) at = tomb;
-    if (c == 0) c = slot_claim(t, i, TAG_EMPTY, tag, key, unit);
+    if (c == 0 && !end) c = slot_claim(t, i, TAG_EMPTY, tag, key, unit);
     if (c > 0 && at < 0) at = (int64_t)i;
     if (c < 0) {
       atomicOr(err, ERR_ARENA_FULL);
@@ -5105,10 +5136,12 @@ __device__ inline bool win_alive(const Win& w, uint32_t now) {
   return w.ws != WS_INVALID && (now <= w.expire || now < w.lc);
 }
 
+// evicted[0]: slots swept; evicted[1]: slots not empty afterwards (live or tombstone).
 __global__ __launch_bounds__(256) void k_sweep(TableDev t, uint64_t nslots, uint32_t now, unsigned long long* evicted) {
-  uint32_t local = 0;
+  uint32_t local = 0, used = 0;
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * 256) {
     Slot* s = &t.slots[i];
+    used += s->tag != TAG_EMPTY;
     if (s->tag < 2) continue;
     bool alive = win_alive(s->cur, now);
     if (!alive)
@@ -5122,6 +5155,7 @@ __global__ __launch_bounds__(256) void k_sweep(TableDev t, uint64_t nslots, uint
     local++;
   }
   if (local) atomicAdd(evicted, (unsigned long long)local);
+  if (used) atomicAdd(evicted + 1, (unsigned long long)used);
 }
 
 // Long-stem arena compaction (rl_sweep, after k_sweep): every live slot's
@@ -5141,6 +5175,65 @@ __global__ __launch_bounds__(256) void k_arena_compact(Slot* slots, uint64_t nsl
     for (uint32_t k = 0; k < n16; k++) dst[k] = src[k];
     sd[SLOT_EXT_DW] = (uint32_t)off;
   }
+}
+
+// Tombstone reclamation (rl_sweep, after k_sweep and the arena's compaction,
+// on a table short of empty slots). A probe for a key walks from its home to
+// its slot and may meet no empty slot before it, so a tombstone is needed
+// while it lies in [home, slot) of some live (stem, unit); every other one
+// becomes an empty slot again, where misses end and inserts land.
+// k_reclaim_mark: every live slot hashes its stem again (the slot's bytes,
+// then the arena's; the home does not depend on the unit) and sets the bits of
+// [home, slot) in a bitmap of one bit per slot. A slot whose tag the hash does
+// not give back (never expected: the table and its hash key belong together)
+// is counted in *bad, and the call then frees nothing.
+// k_reclaim_free: the tombstones without a bit become TAG_EMPTY; *freed counts them.
+__global__ __launch_bounds__(256) void k_reclaim_mark(const TableDev t, const HashKey hk, uint64_t nslots,
+                                                      uint32_t* __restrict__ need, unsigned long long* bad) {
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * 256) {
+    const Slot* s = &t.slots[i];
+    if (s->tag < 2) continue;
+    const uint32_t len = s->key_len, il = slot_inline(len);
+    const uint8_t* ek = len > KEY_IN ? t.arena + (size_t)slot_ext(s) * 16 : nullptr;
+    auto rd = [&](uint32_t a) {  // stem bytes [a, a + 8), zero past the stem
+      uint64_t w = 0;
+      for (uint32_t k = 0; k < 8 && a + k < len; k++) {
+        const uint32_t at = a + k;
+        w |= (uint64_t)(at < il ? s->key[at] : ek[at - KEY_SPLIT]) << (8 * k);
+      }
+      return w;
+    };
+    uint64_t h = hash_stem(hk, rd, 0u, len);
+    if ((uint32_t)(h >> 32) == KEY_DUP) h = ((uint64_t)(KEY_DUP - 1u) << 32) | (uint32_t)h;  // (as k_prepare homes it)
+    const uint64_t dist = (i - (h >> t.shift)) & t.mask;
+    if (slot_tag(h, s->unit) != s->tag || dist >= t.max_probe) {
+      atomicAdd(bad, 1ull);
+      continue;
+    }
+    // bits [j, i) going up from the home, whole words where the range covers them
+    uint64_t j = h >> t.shift;
+    for (uint64_t left = dist; left;) {
+      const uint32_t bit = (uint32_t)(j & 31u);
+      const uint64_t room = nslots - j < 32u - bit ? nslots - j : 32u - bit;  // (to the word's or the table's end)
+      const uint32_t n = (uint32_t)(left < room ? left : room);
+      const uint32_t m = (n == 32u ? 0xFFFFFFFFu : (1u << n) - 1u) << bit;
+      atomicOr(&need[j >> 5], m);
+      j = (j + n) & t.mask;
+      left -= n;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_reclaim_free(Slot* slots, uint64_t nslots, const uint32_t* __restrict__ need,
+                                                      const unsigned long long* bad, unsigned long long* freed) {
+  if (*bad) return;
+  uint32_t local = 0;
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * 256) {
+    if (slots[i].tag != TAG_TOMB || ((need[i >> 5] >> (i & 31u)) & 1u)) continue;
+    slots[i].tag = TAG_EMPTY;
+    local++;
+  }
+  if (local) atomicAdd(freed, (unsigned long long)local);
 }
 
 __global__ __launch_bounds__(256) void k_table_info(const Slot* slots, uint64_t nslots, unsigned long long* out) {
@@ -5759,6 +5852,13 @@ void launch_sweep(const TableDev& t, uint64_t nslots, uint32_t now, unsigned lon
 void launch_arena_compact(Slot* slots, uint64_t nslots, const uint8_t* from, uint8_t* to, unsigned long long* used16,
                           hipStream_t st) {
   k_arena_compact<<<2048, 256, 0, st>>>(slots, nslots, from, to, used16);
+}
+
+// need: (nslots + 31) / 32 zeroed words; ctr[0] = slots whose hash disagrees (zeroed), ctr[1] += tombstones freed
+void launch_reclaim(const TableDev& t, const HashKey& hk, uint64_t nslots, uint32_t* need, unsigned long long* ctr,
+                    hipStream_t st) {
+  k_reclaim_mark<<<2048, 256, 0, st>>>(t, hk, nslots, need, ctr);
+  k_reclaim_free<<<2048, 256, 0, st>>>(t.slots, nslots, need, ctr, ctr + 1);
 }
 
 void launch_lc_count(const TableDev& t, uint64_t nslots, uint32_t now, unsigned long long* out, hipStream_t st) {
