@@ -1117,6 +1117,61 @@ typedef struct rl_hot_info {
 } rl_hot_info;
 int rl_hot_keys(rl_ctx* ctx, const rl_hot_query* q, rl_records* out, rl_hot_info* info);
 
+/* ---- Grow or shrink the counter table in place (a Redis dict's rehash) -------
+ * rl_resize gives every shard of the ctx a table of `table_slots` slots and
+ * places every live key in it on the device: nothing crosses to the host, the
+ * ctx, its threads' handles, its config trie, gauges and counters stay. The
+ * answer to RL_E_TABLE_FULL that needs no second ctx (rl_export_range +
+ * rl_import remain the tools for re-keying and resharding).
+ *
+ * Size: table_slots is the new per-shard slot count, a power of two as
+ * rl_create accepts it, from 2 to 2^32 (a slot index is a 32-bit word of the
+ * history log), else RL_E_INVALID. It may be larger than, smaller than or
+ * equal to the current count; equal is a full rehash that drops every
+ * tombstone.
+ *
+ * Ordering: the call orders after every submitted batch (it completes pending
+ * second halves of the packed and wire paths, host-fed batches and the
+ * progress ring, as rl_export_range does), is synchronous and holds the batch
+ * pipeline for its duration. RL_E_INVALID on a ctx that joined a communicator.
+ *
+ * Preserved: every live key keeps its 64-B slot image verbatim (tag, length,
+ * unit, flags including the exact-path flag, the newest window record, the
+ * chain head, stem bytes or arena offset). The long-stem arena and the history
+ * log keep their size and contents, but for the `slot` word of the entries on
+ * live keys' chains, which is re-pointed at the key's new slot. Untouched:
+ * history_entries, history_appended / _lost / _refused, the sweep floor, the
+ * local-cache gauges, batches, decisions, the loaded config and the hash key.
+ * After success rl_table_info.table_slots is the new count and tombstones is
+ * 0; live_slots, exact_stems, history_slots and arena_bytes_used are as
+ * before; rl_snapshot_size follows the new count, and a snapshot of the ctx
+ * loads into a fresh ctx created with the new table_slots.
+ *
+ * A failed call leaves the ctx exactly as it was (the same slot array, the
+ * same log bytes, the same info):
+ *   RL_E_TABLE_FULL  some key finds no free slot within min(table_slots,
+ *                    65536) slots of its new home (found by the placement on
+ *                    the device; more live slots than table_slots fails early);
+ *   RL_E_HIP         the new table cannot be allocated: the old and the new
+ *                    table (and 4 bytes per old slot) coexist during the call;
+ *   RL_E_INTERNAL    a live slot's tag is not what its stem hashes to.
+ * The log is re-pointed only after every key of every shard has been placed.
+ * (A device failure after that point, which no input can cause, is RL_E_HIP
+ * and leaves the ctx unusable, like any failed kernel.)
+ *
+ * Multi-shard ctx: every shard resizes to table_slots on its own device,
+ * concurrently; no shard changes unless all placed. *info (optional) is summed
+ * over the shards, longest_probe the maximum. */
+typedef struct rl_resize_info {
+  uint64_t slots_before, slots_after;   /* per call: summed over shards */
+  uint64_t keys;                        /* live (stem, unit) slots placed in the new table */
+  uint64_t tombstones_dropped;          /* tombstones of the old table (the new one has none) */
+  uint64_t log_entries_relinked;        /* history-log entries re-pointed at their key's new slot */
+  uint32_t longest_probe;               /* largest home-to-slot distance in the new table */
+  uint32_t reserved;
+} rl_resize_info;
+int rl_resize(rl_ctx* ctx, uint64_t table_slots, rl_resize_info* info /* may be NULL */);
+
 /* Per-stage device timing (HIP events on the batch stream), for benchmarks.
  * rl_profile(ctx, k) with k >= 1 starts accumulating over every k-th batch,
  * the first sampled one being the k-th submitted after the call (1 = every

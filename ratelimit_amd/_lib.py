@@ -24,7 +24,7 @@ EXPORTS = ["rl_abi_version", "rl_create", "rl_destroy", "rl_last_error", "rl_do_
            "rl_debug_log_tear", "rl_export_range", "rl_import", "rl_lookup", "rl_do_limit_requests_verdict",
            "rl_debug_verdict", "rl_request_batch_pack", "rl_do_limit_requests_packed_async",
            "rl_do_limit_wire_async", "rl_response_bound", "rl_do_limit_wire_respond_async", "rl_response_serialize",
-           "rl_debug_respond", "rl_hot_keys"]
+           "rl_debug_respond", "rl_hot_keys", "rl_resize"]
 
 _libs = {}
 
@@ -123,6 +123,8 @@ def load(path):
     if hasattr(L, "rl_hot_keys"):
         L.rl_hot_keys.argtypes = [C.c_void_p, C.POINTER(abi.RlHotQuery), C.POINTER(abi.RlRecords),
                                   C.POINTER(abi.RlHotInfo)]
+    if hasattr(L, "rl_resize"):  # (A/B runs load the parent's library)
+        L.rl_resize.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(abi.RlResizeInfo)]
     if hasattr(L, "rl_do_limit_requests_verdict"):
         L.rl_do_limit_requests_verdict.argtypes = [C.c_void_p, C.POINTER(abi.RlRequestBatch),
                                                    C.POINTER(abi.RlRequestResult), C.c_uint32,

@@ -250,6 +250,14 @@ class RlHotInfo(C.Structure):
     _fields_ = [("slots", C.c_uint64), ("matched", C.c_uint64), ("hits", C.c_uint64), ("above", C.c_uint64),
                 ("threshold", C.c_uint32), ("reserved", C.c_uint32), ("time_floor", C.c_int64)]
 
+
+class RlResizeInfo(C.Structure):
+    """rl_resize_info: what one rl_resize moved (summed over shards; longest_probe the maximum)."""
+    _fields_ = [("slots_before", C.c_uint64), ("slots_after", C.c_uint64), ("keys", C.c_uint64),
+                ("tombstones_dropped", C.c_uint64), ("log_entries_relinked", C.c_uint64),
+                ("longest_probe", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 RL_MATCH_NONE, RL_MATCH_UNLIMITED, RL_MATCH_LIMIT = 0, 1, 2
 REQUEST_ARRAYS = ("domain_bytes", "domain_off", "now", "hits", "req_idx", "entry_first", "desc_off", "desc_bytes",
                   "key_len", "value_len", "override_flags", "override_rpu", "override_unit", "override_rule")

@@ -49,7 +49,7 @@ constexpr uint32_t MAX_LOCAL_SHARDS = 16;
 
 // One shard's worker: runs its router's collective steps on its own thread.
 struct ShardWorker {
-  enum Job { IDLE, BATCH, SYNC, EXIT };
+  enum Job { IDLE, BATCH, SYNC, RESIZE, EXIT };
   std::thread th;
   std::mutex mu;
   std::condition_variable cv;
@@ -58,6 +58,8 @@ struct ShardWorker {
   rl_result out{};
   CommIO io{};
   hipStream_t caller = nullptr;
+  uint64_t rs_slots = 0;  // RESIZE: the new slot count, and what the shard placed
+  ResizePlan rs_plan;
   int rc = RL_OK;
 };
 
@@ -129,6 +131,8 @@ void worker_main(rl_ctx* c, uint32_t j) {
     int rc = RL_OK;
     if (job == ShardWorker::BATCH) {
       rc = comm_do_limit(c->r[j], c->e[j], &w.in, &w.out, w.caller, &w.io);
+    } else if (job == ShardWorker::RESIZE) {  // (the placement only: rl_resize commits once every shard has placed)
+      rc = eng_resize_place(c->e[j], w.rs_slots, &w.rs_plan);
     } else {  // SYNC: the pending batch (collective), the router's streams, then the engine's error words
       rc = comm_synchronize(c->r[j], c->e[j]);
       const int re = eng_synchronize(c->e[j]);
@@ -774,6 +778,40 @@ int rl_export_range(rl_ctx* c, uint32_t shard, uint64_t slot_begin, uint64_t slo
   if (shard >= c->n) return fail(c, RL_E_INVALID, "gpu: bad shard");
   if (const int src = settle_local(c)) return src;
   return from_engine(c, c->e[shard], eng_export_range(c->e[shard], slot_begin, slot_end, out, info));
+}
+
+int rl_resize(rl_ctx* c, uint64_t table_slots, rl_resize_info* info) {
+  // (a single-shard ctx reports through its engine: rl_last_error reads it there)
+  auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };
+  if (!c) return bad(RL_E_INVALID, "gpu: null ctx");
+  if (c->comm) return bad(RL_E_INVALID, "gpu: rl_resize is not for a ctx that joined a communicator");
+  if (const int rc = from_engine(c, c->e[0], eng_resize_check(c->e[0], table_slots))) return rc;
+  if (c->n == 1) {
+    const int rc = eng_resize(c->e[0], table_slots, info);
+    if (!rc) c->cfg.table_slots = table_slots;
+    return rc;
+  }
+  if (const int src = settle_local(c)) return src;
+  // every shard places its keys in a new table on its own device and worker;
+  // nothing of any shard has changed until all of them have succeeded
+  for (uint32_t j = 0; j < c->n; j++) c->w[j].rs_slots = table_slots;
+  int rc = run_shards(c, ShardWorker::RESIZE);
+  rl_resize_info sum{};
+  for (uint32_t j = 0; j < c->n && !rc; j++) {
+    rc = from_engine(c, c->e[j], eng_resize_commit(c->e[j], &c->w[j].rs_plan));
+    const rl_resize_info& x = c->w[j].rs_plan.info;
+    sum.slots_before += x.slots_before;
+    sum.slots_after += x.slots_after;
+    sum.keys += x.keys;
+    sum.tombstones_dropped += x.tombstones_dropped;
+    sum.log_entries_relinked += x.log_entries_relinked;
+    sum.longest_probe = std::max(sum.longest_probe, x.longest_probe);
+  }
+  for (uint32_t j = 0; j < c->n; j++) eng_resize_abort(c->e[j], &c->w[j].rs_plan);  // (what was not committed)
+  if (rc) return rc;
+  c->cfg.table_slots = table_slots;
+  if (info) *info = sum;
+  return RL_OK;
 }
 
 int rl_import(rl_ctx* c, const rl_records* in) {

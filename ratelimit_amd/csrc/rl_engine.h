@@ -332,6 +332,24 @@ struct HotAnswer {
 };
 int eng_hot_check(Engine* c, const rl_hot_query* q);
 int eng_hot_keys(Engine* c, const rl_hot_query* q, HotAnswer* ans, rl_hot_info* info);
+// rl_resize on this engine. One call (eng_resize), or in two steps for a ctx of
+// several shards: eng_resize_place puts every live key into a new table beside
+// the old one and changes nothing of the engine (any failure leaves the plan
+// empty); once every shard has placed, eng_resize_commit re-points the history
+// log, swaps the tables and frees the old one (p->info is then complete), else
+// eng_resize_abort frees what was placed. eng_resize_check: the size alone.
+struct ResizePlan {
+  Slot* slots = nullptr;              // the new table (after the commit's swap: the old one)
+  uint32_t* map = nullptr;            // [old nslots] new index of each live old slot
+  unsigned long long* ctr = nullptr;  // [RESIZE_CTR_WORDS]
+  uint64_t nslots = 0;
+  rl_resize_info info{};
+};
+int eng_resize_check(Engine* c, uint64_t table_slots);
+int eng_resize_place(Engine* c, uint64_t table_slots, ResizePlan* p);
+int eng_resize_commit(Engine* c, ResizePlan* p);
+void eng_resize_abort(Engine* c, ResizePlan* p);
+int eng_resize(Engine* c, uint64_t table_slots, rl_resize_info* info);
 
 // Owner side of a routed batch, pipelined on the engine's streams like
 // eng_do_limit_async: unpack the n received wire records (chunks of n_src

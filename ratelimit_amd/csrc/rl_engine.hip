@@ -3078,4 +3078,106 @@ int eng_lookup(Engine* c, const rl_keys* in, rl_key_state* out) {
   return RL_OK;
 }
 
+// ---------------------------------------------------------------------------
+// rl_resize on one engine, in two steps so that a multi-shard ctx commits only
+// once every shard has placed its keys. eng_resize_place drains the pipeline,
+// allocates and zeroes the new table and runs the placement scan, which only
+// reads the old table: whatever it returns but RL_OK, the engine is as it was
+// and the plan is empty. eng_resize_commit re-points the history log (the one
+// step that writes shared state in place), swaps slots / nslots and frees the
+// old table; eng_resize_abort drops a placed plan instead.
+// ---------------------------------------------------------------------------
+void eng_resize_abort(Engine* c, ResizePlan* p) {
+  if (!p) return;
+  if (c && (p->slots || p->map || p->ctr)) (void)hipSetDevice(c->cfg.device);
+  if (p->slots) (void)hipFree(p->slots);
+  if (p->map) (void)hipFree(p->map);
+  if (p->ctr) (void)hipFree(p->ctr);
+  *p = ResizePlan{};
+}
+
+int eng_resize_check(Engine* c, uint64_t table_slots) {
+  if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
+  if (table_slots < 2 || (table_slots & (table_slots - 1)) || table_slots > (1ull << 32))
+    return set_err(c, RL_E_INVALID, "gpu: rl_resize: table_slots must be a power of two in [2, 2^32]");
+  return RL_OK;
+}
+
+int eng_resize_place(Engine* c, uint64_t table_slots, ResizePlan* p) {
+  if (!p) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  *p = ResizePlan{};
+  if (const int rc = eng_resize_check(c, table_slots)) return rc;
+  RQ_SETTLE(c);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream;
+  HIPCHK(c, after_batches(c, st));
+  hipError_t e = dalloc(&p->slots, table_slots);
+  if (e == hipSuccess) e = dalloc(&p->map, c->nslots);
+  if (e == hipSuccess) e = dalloc(&p->ctr, RESIZE_CTR_WORDS);
+  if (e == hipSuccess) e = hipMemsetAsync(p->slots, 0, table_slots * sizeof(Slot), st);
+  if (e == hipSuccess) e = hipMemsetAsync(p->ctr, 0, RESIZE_CTR_WORDS * 8, st);
+  unsigned long long h[RESIZE_CTR_WORDS] = {};
+  if (e == hipSuccess) {
+    launch_resize_place(table_view(c), c->hk, c->nslots, p->slots, table_slots, p->map, p->ctr, st);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h, p->ctr, sizeof(h), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();  // (an allocation that failed is this call's error, not the next one's)
+    eng_resize_abort(c, p);
+    return set_err(c, RL_E_HIP, std::string("gpu: rl_resize: ") + hipGetErrorString(e) +
+                                    " (the old and the new table coexist during the call)");
+  }
+  if (h[2]) {
+    eng_resize_abort(c, p);
+    return set_err(c, RL_E_INTERNAL, "gpu: rl_resize: " + std::to_string(h[2]) +
+                                         " live slots whose stem does not hash to their tag and place");
+  }
+  if (h[3]) {
+    eng_resize_abort(c, p);
+    return set_err(c, RL_E_TABLE_FULL, "gpu: rl_resize: " + std::to_string(h[3]) + " of " + std::to_string(h[0] + h[3]) +
+                                           " keys find no free slot within their probe window of a table of " +
+                                           std::to_string(table_slots) + " slots");
+  }
+  p->nslots = table_slots;
+  p->info.slots_before = c->nslots;
+  p->info.slots_after = table_slots;
+  p->info.keys = h[0];
+  p->info.tombstones_dropped = h[1];
+  p->info.longest_probe = (uint32_t)h[4];
+  return RL_OK;
+}
+
+int eng_resize_commit(Engine* c, ResizePlan* p) {
+  if (!c || !p || !p->slots) return set_err(c, RL_E_INVALID, "gpu: rl_resize: nothing placed");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream;
+  unsigned long long relinked = 0;
+  launch_resize_relink(table_view(c), c->nslots, p->map, p->ctr, st);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(&relinked, p->ctr + 5, 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {  // (a failed kernel: the device's state is lost either way)
+    eng_resize_abort(c, p);
+    return set_err(c, RL_E_HIP, std::string("gpu: rl_resize: re-link: ") + hipGetErrorString(e));
+  }
+  p->info.log_entries_relinked = relinked;
+  std::swap(c->slots, p->slots);  // (the plan now holds the old table: freed below)
+  c->nslots = p->nslots;
+  c->cfg.table_slots = p->nslots;
+  const rl_resize_info info = p->info;
+  eng_resize_abort(c, p);
+  p->info = info;
+  return RL_OK;
+}
+
+int eng_resize(Engine* c, uint64_t table_slots, rl_resize_info* info) {
+  ResizePlan p;
+  if (const int rc = eng_resize_place(c, table_slots, &p)) return rc;
+  if (const int rc = eng_resize_commit(c, &p)) return rc;
+  if (info) *info = p.info;
+  return RL_OK;
+}
+
 }  // namespace rl

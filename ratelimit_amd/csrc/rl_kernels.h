@@ -392,6 +392,20 @@ void launch_reclaim(const TableDev& t, const HashKey& hk, uint64_t nslots, uint3
                     hipStream_t st);
 void launch_lc_count(const TableDev& t, uint64_t nslots, uint32_t now, unsigned long long* out, hipStream_t st);
 void launch_table_info(const Slot* slots, uint64_t nslots, unsigned long long* out, hipStream_t st);
+// ---- in-place resize (rl_resize): two scans of the old table ----
+// Place every live slot of t (nslots slots) in `to` (to_nslots slots, a power
+// of two, zeroed; its probe window min(to_nslots, 65536)); map[i] = the new
+// index of live old slot i. ctr (RESIZE_CTR_WORDS zeroed words): [0] keys
+// placed, [1] tombstones met, [2] slots whose hash disagrees with their tag,
+// [3] keys without a slot in their window, [4] the longest probe. Only `to`,
+// map and ctr are written.
+constexpr uint32_t RESIZE_CTR_WORDS = 6;
+void launch_resize_place(const TableDev& t, const HashKey& hk, uint64_t nslots, Slot* to, uint64_t to_nslots,
+                         uint32_t* map, unsigned long long* ctr, hipStream_t st);
+// The history-log entries on the chains of t's live slots get map[slot] as
+// their `slot` word; ctr[5] += entries stored. (t: still the OLD table.)
+void launch_resize_relink(const TableDev& t, uint64_t nslots, const uint32_t* map, unsigned long long* ctr,
+                          hipStream_t st);
 // ---- export / import of window records (rl_export_range, rl_import) ----
 // Device staging of one export call: the rl_records arrays (off: the records'
 // stem offsets; the host appends the total).

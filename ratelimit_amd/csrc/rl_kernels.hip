@@ -5081,11 +5081,13 @@ __global__ __launch_bounds__(256) void k_finish(const unsigned long long* __rest
   }
 }
 
-// Walk slot s's history chain: f(entry record, hop index) for each entry the
-// log still holds, newest first (stops where one was overwritten, or when f says so).
+// Walk the history chain of slot si (tag `tag`, chain head `head`, newest window
+// cur_ws): f(entry, hop index) for each entry the log still holds, newest
+// first (stops where one was overwritten, or when f says so). f may store to
+// the entry's `slot` word (the resize's re-link): its other words are read first.
 template <typename F>
-__device__ inline void chain_walk(const TableDev& t, uint32_t si, const Slot& s, F f) {
-  uint32_t ptr = s.ring, tprev = s.cur.ws, saved = LOG_NONE, power = 1, lam = 0;
+__device__ inline void chain_walk_ent(const TableDev& t, uint32_t si, uint32_t tag, uint32_t head, uint32_t cur_ws, F f) {
+  uint32_t ptr = head, tprev = cur_ws, saved = LOG_NONE, power = 1, lam = 0;
   for (uint32_t hops = 0; ptr != LOG_NONE && hops < LOG_MAX_HOPS && ptr != saved; hops++) {  // (log_find's checks)
     const uint32_t pos = ptr & LOG_POS_MASK;
     if (pos >= t.log_cap) return;
@@ -5094,12 +5096,19 @@ __device__ inline void chain_walk(const TableDev& t, uint32_t si, const Slot& s,
       power <<= 1;
       lam = 0;
     }
-    const LogEnt& e = t.log[(size_t)(ptr >> LOG_POS_BITS) * t.log_cap + pos];
-    if (e.slot != si || e.tag != s.tag || e.t_app > tprev) return;
-    if (!f(e.w, hops)) return;
-    tprev = e.t_app;
-    ptr = e.prev;
+    LogEnt& e = t.log[(size_t)(ptr >> LOG_POS_BITS) * t.log_cap + pos];
+    if (e.slot != si || e.tag != tag || e.t_app > tprev) return;
+    const uint32_t t_app = e.t_app, prev = e.prev;
+    if (!f(e, hops)) return;
+    tprev = t_app;
+    ptr = prev;
   }
+}
+
+// ... of slot s, f(entry record, hop index).
+template <typename F>
+__device__ inline void chain_walk(const TableDev& t, uint32_t si, const Slot& s, F f) {
+  chain_walk_ent(t, si, s.tag, s.ring, s.cur.ws, [&](LogEnt& e, uint32_t hops) { return f(e.w, hops); });
 }
 
 // Keys in the local over-limit cache at `now` (freecache EntryCount of live
@@ -5177,6 +5186,24 @@ __global__ __launch_bounds__(256) void k_arena_compact(Slot* slots, uint64_t nsl
   }
 }
 
+// The stem hash of a live slot from its stored bytes (the slot's, then the
+// arena's), with k_prepare's KEY_DUP remap: what homed the slot and gave its tag.
+__device__ inline uint64_t slot_stem_hash(const TableDev& t, const HashKey& hk, const Slot* s) {
+  const uint32_t len = s->key_len, il = slot_inline(len);
+  const uint8_t* ek = len > KEY_IN ? t.arena + (size_t)slot_ext(s) * 16 : nullptr;
+  auto rd = [&](uint32_t a) {  // stem bytes [a, a + 8), zero past the stem
+    uint64_t w = 0;
+    for (uint32_t k = 0; k < 8 && a + k < len; k++) {
+      const uint32_t at = a + k;
+      w |= (uint64_t)(at < il ? s->key[at] : ek[at - KEY_SPLIT]) << (8 * k);
+    }
+    return w;
+  };
+  uint64_t h = hash_stem(hk, rd, 0u, len);
+  if ((uint32_t)(h >> 32) == KEY_DUP) h = ((uint64_t)(KEY_DUP - 1u) << 32) | (uint32_t)h;  // (as k_prepare homes it)
+  return h;
+}
+
 // Tombstone reclamation (rl_sweep, after k_sweep and the arena's compaction,
 // on a table short of empty slots). A probe for a key walks from its home to
 // its slot and may meet no empty slot before it, so a tombstone is needed
@@ -5193,18 +5220,7 @@ __global__ __launch_bounds__(256) void k_reclaim_mark(const TableDev t, const Ha
   for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * 256) {
     const Slot* s = &t.slots[i];
     if (s->tag < 2) continue;
-    const uint32_t len = s->key_len, il = slot_inline(len);
-    const uint8_t* ek = len > KEY_IN ? t.arena + (size_t)slot_ext(s) * 16 : nullptr;
-    auto rd = [&](uint32_t a) {  // stem bytes [a, a + 8), zero past the stem
-      uint64_t w = 0;
-      for (uint32_t k = 0; k < 8 && a + k < len; k++) {
-        const uint32_t at = a + k;
-        w |= (uint64_t)(at < il ? s->key[at] : ek[at - KEY_SPLIT]) << (8 * k);
-      }
-      return w;
-    };
-    uint64_t h = hash_stem(hk, rd, 0u, len);
-    if ((uint32_t)(h >> 32) == KEY_DUP) h = ((uint64_t)(KEY_DUP - 1u) << 32) | (uint32_t)h;  // (as k_prepare homes it)
+    const uint64_t h = slot_stem_hash(t, hk, s);
     const uint64_t dist = (i - (h >> t.shift)) & t.mask;
     if (slot_tag(h, s->unit) != s->tag || dist >= t.max_probe) {
       atomicAdd(bad, 1ull);
@@ -5251,6 +5267,112 @@ __global__ __launch_bounds__(256) void k_table_info(const Slot* slots, uint64_t 
   if (tomb) atomicAdd(&out[1], (unsigned long long)tomb);
   if (exact) atomicAdd(&out[2], (unsigned long long)exact);
   if (hist) atomicAdd(&out[3], (unsigned long long)hist);
+}
+
+// ===========================================================================
+// In-place resize (rl_resize): every live slot of the old table is placed in a
+// zeroed table of another size, then the history log's entries on live chains
+// are re-pointed at their keys' new slots. Two scans of the old table, the
+// kernel boundary between them the only synchronisation.
+//
+// k_resize_place: consecutive lanes read consecutive 64-B slots (a wave reads
+// 4 KB contiguous). A live slot hashes its stem again (slot_stem_hash), checks
+// the tag and its place in the old table (k_reclaim_mark's *bad case), and
+// claims the first empty slot from its new home with a CAS on the tag word;
+// the slot's other 60 bytes follow with vector stores. Source keys are
+// distinct, so no stem is compared; nothing is ever emptied, so a key's path
+// from its home to its slot holds no empty slot and a stem's unit slots (one
+// home) lie on one unbroken run. map[i] = the new index of old slot i (live
+// slots only). ctr: [0] keys placed, [1] tombstones met, [2] slots whose tag
+// or place disagrees with their hash, [3] keys that found no slot within
+// to_probe, [4] the longest home-to-slot distance. The old table is only read.
+// ===========================================================================
+__global__ __launch_bounds__(256) void k_resize_place(const TableDev t, const HashKey hk, uint64_t nslots, Slot* to,
+                                                      uint64_t to_mask, uint32_t to_shift, uint32_t to_probe,
+                                                      uint32_t* __restrict__ map, unsigned long long* ctr) {
+  unsigned long long v[4] = {0, 0, 0, 0};
+  uint32_t far = 0;
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * 256) {
+    SlotImg im;
+    load_img_lo(&t.slots[i], im);
+    const uint32_t tag = im.tag();
+    if (tag < 2) {
+      v[1] += tag == TAG_TOMB;
+      continue;
+    }
+    const uint64_t h = slot_stem_hash(t, hk, &t.slots[i]);
+    if (slot_tag(h, im.unit()) != tag || ((i - (h >> t.shift)) & t.mask) >= t.max_probe) {
+      v[2]++;
+      continue;
+    }
+    uint64_t j = h >> to_shift;
+    uint32_t p = 0;
+    for (; p < to_probe; p++, j = (j + 1) & to_mask) {
+      uint32_t* tg = &to[j].tag;
+      if (__hip_atomic_load(tg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != TAG_EMPTY) continue;
+      if (atomicCAS(tg, TAG_EMPTY, tag) == TAG_EMPTY) break;
+    }
+    if (p == to_probe) {
+      v[3]++;
+      continue;
+    }
+    uint32_t* d = reinterpret_cast<uint32_t*>(&to[j]);
+    d[1] = im.v[0].y;
+    *reinterpret_cast<uint2*>(d + 2) = make_uint2(im.v[0].z, im.v[0].w);
+#pragma unroll
+    for (int k = 1; k < 4; k++) reinterpret_cast<uint4*>(d)[k] = im.v[k];
+    map[i] = (uint32_t)j;
+    v[0]++;
+    far = p > far ? p : far;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const uint32_t o = __shfl_xor(far, m);
+    far = o > far ? o : far;
+  }
+  __shared__ unsigned long long sh[4][4];
+  __shared__ uint32_t shf[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const unsigned long long x = wave_sum(v[k]);
+    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6][k] = x;
+  }
+  if ((threadIdx.x & 63u) == 0) shf[threadIdx.x >> 6] = far;
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const unsigned long long x = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    if (x) atomicAdd(&ctr[threadIdx.x], x);
+  } else if (threadIdx.x == 4) {
+    uint32_t x = shf[0];
+    for (int k = 1; k < 4; k++) x = shf[k] > x ? shf[k] : x;
+    if (x) atomicMax(&ctr[4], (unsigned long long)x);
+  }
+}
+
+// The re-link, launched only once every key (of every shard) has its new slot:
+// each live old slot with a chain walks it under log_find's owner and t_app
+// checks (chain_walk_ent, on the OLD index and the tag) and stores its new
+// index into every entry it owns. Entries no live chain reaches stay as they
+// are. ctr[5] += the entries stored.
+__global__ __launch_bounds__(256) void k_resize_relink(const TableDev t, uint64_t nslots,
+                                                       const uint32_t* __restrict__ map, unsigned long long* ctr) {
+  unsigned long long n = 0;
+  for (uint64_t i = blockIdx.x * 256ull + threadIdx.x; i < nslots; i += (uint64_t)gridDim.x * 256) {
+    SlotImg im;
+    load_img_head(&t.slots[i], im);
+    if (im.tag() < 2 || im.ring() == RING_NONE) continue;
+    const uint32_t to = map[i];
+    chain_walk_ent(t, (uint32_t)i, im.tag(), im.ring(), im.cur().ws, [&](LogEnt& e, uint32_t) {
+      e.slot = to;
+      n++;
+      return true;
+    });
+  }
+  __shared__ unsigned long long sh[4];
+  n = wave_sum(n);
+  if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0 && sh[0] + sh[1] + sh[2] + sh[3]) atomicAdd(&ctr[5], sh[0] + sh[1] + sh[2] + sh[3]);
 }
 
 // ===========================================================================
@@ -5867,6 +5989,19 @@ void launch_lc_count(const TableDev& t, uint64_t nslots, uint32_t now, unsigned 
 
 void launch_table_info(const Slot* slots, uint64_t nslots, unsigned long long* out, hipStream_t st) {
   k_table_info<<<2048, 256, 0, st>>>(slots, nslots, out);
+}
+
+void launch_resize_place(const TableDev& t, const HashKey& hk, uint64_t nslots, Slot* to, uint64_t to_nslots,
+                         uint32_t* map, unsigned long long* ctr, hipStream_t st) {
+  const uint32_t probe = (uint32_t)(to_nslots < (1u << 16) ? to_nslots : (1u << 16));
+  k_resize_place<<<(uint32_t)((nslots + 255) / 256 < 2048 ? (nslots + 255) / 256 : 2048), 256, 0, st>>>(
+      t, hk, nslots, to, to_nslots - 1, 64u - (uint32_t)__builtin_ctzll(to_nslots), probe, map, ctr);
+}
+
+void launch_resize_relink(const TableDev& t, uint64_t nslots, const uint32_t* map, unsigned long long* ctr,
+                          hipStream_t st) {
+  k_resize_relink<<<(uint32_t)((nslots + 255) / 256 < 2048 ? (nslots + 255) / 256 : 2048), 256, 0, st>>>(t, nslots, map,
+                                                                                                        ctr);
 }
 
 void launch_export_count(const TableDev& t, uint64_t s0, uint64_t s1, uint32_t* cnt, unsigned long long* tot,

@@ -606,6 +606,17 @@ class Backend:
         buf = np.ascontiguousarray(buf, np.uint8)
         self._check(self.L.rl_snapshot_load(self.ctx, abi.ptr(buf), buf.size))
 
+    def resize(self, table_slots: int) -> dict:
+        """rl_resize: every shard's table becomes table_slots slots (a power of two;
+        larger, smaller or equal: equal drops the tombstones), every live key placed
+        in it on the device, the ctx and all its other state kept. Returns the
+        rl_resize_info fields. Raises RedisError with the call's status
+        (RL_E_TABLE_FULL: the keys do not fit) and leaves the table as it was."""
+        info = abi.RlResizeInfo()
+        self._check(self.L.rl_resize(self.ctx, table_slots, C.byref(info)))
+        self.cfg.table_slots = table_slots
+        return {f: getattr(info, f) for f, _ in abi.RlResizeInfo._fields_ if f != "reserved"}
+
     # ---- export / import of live counters (resize, reshard, re-key)
     def n_shards(self) -> int:
         return max(int(self.cfg.n_shards), 1)
