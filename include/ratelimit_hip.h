@@ -760,7 +760,8 @@ int rl_do_limit_requests_packed_async(rl_ctx* ctx, const rl_request_batch_packed
  *  - RL_WIRE_MALFORMED exactly where rl_packer_pack on that message alone
  *    returns RL_E_INVALID;
  *  - RL_WIRE_DEFERRED for a well-formed message that carries a descriptor with
- *    `limit` (its stats key is a host-interned string) or exceeds the packed
+ *    `limit` (its stats key is a host-interned string; see
+ *    rl_override_rules_enable for interning it on the device) or exceeds the packed
  *    layout's per-item limits (more than 65535 descriptors, a descriptor of
  *    more than 65535 entries, a domain over 65535 bytes): the caller resubmits
  *    it through the host packer;
@@ -792,7 +793,7 @@ enum rl_wire_status { RL_WIRE_OK = 0, RL_WIRE_DEFERRED = 1, RL_WIRE_MALFORMED = 
 
 typedef struct rl_wire_batch {
   uint32_t n_requests;
-  uint32_t n_rules;      /* config rule ids are < n_rules (this path carries no override rules) */
+  uint32_t n_rules;      /* config rule ids are < n_rules; with rl_override_rules_enable, override rule ids too */
   const uint8_t* buf;    /* pinned host memory (rl_alloc_host): copied once, asynchronously */
   uint64_t buf_bytes;
   /* sections of buf, byte offsets, each a multiple of 4 */
@@ -812,6 +813,82 @@ typedef struct rl_wire_result {   /* host memory */
 
 int rl_do_limit_wire_async(rl_ctx* ctx, const rl_wire_batch* in, rl_wire_result* wire,
                            rl_request_result* out, uint32_t opts, rl_request_verdict* verdict);
+
+/* ---- Override stats keys interned on the GPU --------------------------------
+ * A descriptor's `limit` override counts under the stats key
+ * descriptorKey(domain, descriptor) (config_impl.go:300-312): domain '.' then,
+ * per entry and joined by '.', key and, when the value is not empty, '_'
+ * value. rl_packer_pack hands those keys dense rule ids on the host, which is
+ * why the wire path defers such messages. rl_override_rules_enable moves that
+ * interning onto the device: the ctx then owns a table of key bytes -> rule id
+ * (ids first_rule, first_rule + 1, ... in the order the device first saw the
+ * keys), and on both wire entry points a well-formed message whose descriptors
+ * carry `limit` is RL_WIRE_OK when every one of its overrides
+ *  - has a unit in 1..4 (another unit keeps the message RL_WIRE_DEFERRED: the
+ *    host path keeps its behaviour for it),
+ *  - has a descriptorKey of at most 65535 bytes,
+ *  - found or was given a rule id r, and
+ *  - r < in->n_rules,
+ * and the message does not repeat a long domain over many overrides (each key
+ * starts with the domain): overrides x (domain bytes + 1) <= 16 x the
+ * message's bytes, which keeps a lane's work linear in its payload.
+ * Otherwise the message is RL_WIRE_DEFERRED exactly as without the feature;
+ * deferred_full counts the messages deferred by the last two conditions (no id
+ * or arena space left, the bounded probe exhausted, r >= n_rules). No failure
+ * of the interner fails a batch or yields a wrong id. For the RL_WIRE_OK
+ * messages the answers, table effects, verdict, responses and stats are those
+ * of rl_do_limit_requests_packed_async on the packer's batch of the same
+ * messages, up to the naming of the override rule ids (compare rows by key).
+ * requests_per_unit and unit merge across repeated `limit` fields as in the
+ * packer; the domain is the message's last field 1.
+ *
+ * Identity is the key's bytes: entry ("a_b", "") and entry ("a", "b") give one
+ * key and one id; two different keys never share an id (the full bytes are
+ * compared; the hash, SipHash-1-3 under the ctx's hash_seed, only places
+ * them). A key keeps its id for the ctx's lifetime. A malformed message
+ * interns nothing; the keys of a batch that later fails at rl_synchronize stay
+ * interned. Which new keys take the last free ids of a full table is
+ * unspecified. An id is handed out even when it is >= the batch's n_rules
+ * (that message is deferred; a later batch with a larger n_rules uses the id).
+ *
+ * The table is process state, like the reference's stats store: it is not part
+ * of rl_snapshot_save / rl_snapshot_load, rl_export_range / rl_import or
+ * rl_resize (which leaves it as it is), and rl_config_load does not move
+ * first_rule: the caller reserves room for the config's rule ids below it.
+ *
+ * rl_override_rules_enable: once per ctx. RL_E_INVALID for a second call,
+ * non-zero reserved fields, capacity == 0, first_rule + capacity > max_rules,
+ * a multi-shard ctx or one that joined a communicator; RL_E_HIP when a device
+ * allocation fails (nothing is enabled then). key_bytes above 2^32 - 1 is
+ * taken as 2^32 - 1 (key_bytes_cap reports it). Without the call nothing
+ * changes: a message with a `limit` is RL_WIRE_DEFERRED.
+ *
+ * rl_override_rules_info_get and rl_override_rule_keys order after every
+ * submitted batch and are synchronous, like rl_lookup; RL_E_INVALID on a ctx
+ * without the feature. rl_override_rule_keys returns the names of the ids
+ * [from_rule, from_rule + n): key i = bytes[off[i], off[i+1]), off holding
+ * n + 1 entries; RL_E_INVALID for a range outside [first_rule, first_rule +
+ * rules); bytes == NULL or cap too small: RL_E_CAPACITY, *needed = the bytes
+ * needed, off filled, no byte written (like rl_response_serialize). An adapter
+ * fetches names only when an output shows a rule_id, or a non-zero stats row,
+ * beyond the names it holds. */
+typedef struct rl_override_rules_config {
+  uint32_t first_rule;   /* ids handed out are first_rule, first_rule + 1, ... */
+  uint32_t capacity;     /* at most this many distinct override stats keys */
+  uint64_t key_bytes;    /* arena for their bytes (0 = 64 * capacity) */
+  uint32_t reserved[4];  /* zero */
+} rl_override_rules_config;
+int rl_override_rules_enable(rl_ctx* ctx, const rl_override_rules_config* cfg);
+
+typedef struct rl_override_rules_info {
+  uint32_t first_rule, capacity, rules /* ids handed out */, reserved;
+  uint64_t key_bytes_used, key_bytes_cap;
+  uint64_t deferred_full;  /* messages deferred because no id / arena space / id >= n_rules */
+} rl_override_rules_info;
+int rl_override_rules_info_get(rl_ctx* ctx, rl_override_rules_info* info);
+
+int rl_override_rule_keys(rl_ctx* ctx, uint32_t from_rule, uint32_t n, uint8_t* bytes, uint64_t cap,
+                          uint32_t* off, uint64_t* needed /* may be NULL */);
 
 /* ---- Serialized responses written on the GPU --------------------------------
  * The way back of the wire path: one serialized

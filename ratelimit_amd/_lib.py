@@ -24,7 +24,8 @@ EXPORTS = ["rl_abi_version", "rl_create", "rl_destroy", "rl_last_error", "rl_do_
            "rl_debug_log_tear", "rl_export_range", "rl_import", "rl_lookup", "rl_do_limit_requests_verdict",
            "rl_debug_verdict", "rl_request_batch_pack", "rl_do_limit_requests_packed_async",
            "rl_do_limit_wire_async", "rl_response_bound", "rl_do_limit_wire_respond_async", "rl_response_serialize",
-           "rl_debug_respond", "rl_hot_keys", "rl_resize"]
+           "rl_debug_respond", "rl_hot_keys", "rl_resize", "rl_override_rules_enable", "rl_override_rules_info_get",
+           "rl_override_rule_keys"]
 
 _libs = {}
 
@@ -154,6 +155,11 @@ def load(path):
         L.rl_debug_respond.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                        C.POINTER(abi.RlRequestResult), C.c_uint32, C.POINTER(abi.RlResponseFormat),
                                        C.POINTER(abi.RlResponseBatch)]
+    if hasattr(L, "rl_override_rules_enable"):  # (A/B runs load the parent's library)
+        L.rl_override_rules_enable.argtypes = [C.c_void_p, C.POINTER(abi.RlOverrideRulesConfig)]
+        L.rl_override_rules_info_get.argtypes = [C.c_void_p, C.POINTER(abi.RlOverrideRulesInfo)]
+        L.rl_override_rule_keys.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                            C.POINTER(C.c_uint64)]
     if L.rl_abi_version() != abi.ABI_VERSION:
         raise RuntimeError("libratelimit_hip.so ABI mismatch")
     _libs[path] = L

@@ -164,6 +164,18 @@ class RlWireResult(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class RlOverrideRulesConfig(C.Structure):
+    """rl_override_rules_config: the rule ids and the room of the device-interned override stats keys."""
+    _fields_ = [("first_rule", C.c_uint32), ("capacity", C.c_uint32), ("key_bytes", C.c_uint64),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class RlOverrideRulesInfo(C.Structure):
+    """rl_override_rules_info: what rl_override_rules_info_get reports."""
+    _fields_ = [("first_rule", C.c_uint32), ("capacity", C.c_uint32), ("rules", C.c_uint32), ("reserved", C.c_uint32),
+                ("key_bytes_used", C.c_uint64), ("key_bytes_cap", C.c_uint64), ("deferred_full", C.c_uint64)]
+
+
 RL_RESPONSE_KEY_MAX = 64  # include/ratelimit_hip.h
 RL_RESPONSE_STATUS_MAX = 26
 

@@ -1051,6 +1051,27 @@ int rl_do_limit_wire_respond_async(rl_ctx* c, const rl_wire_batch* in, rl_wire_r
   return eng_do_limit_wire_async(c->e[0], in, wire, out, opts, verdict, fmt, resp);
 }
 
+int rl_override_rules_enable(rl_ctx* c, const rl_override_rules_config* cfg) {
+  if (!c) return fail(c, RL_E_INVALID, "gpu: null ctx");
+  const char* single = "gpu: rl_override_rules_enable is for single-shard ctxs (the wire paths')";
+  if (c->n > 1) return fail(c, RL_E_INVALID, single);
+  if (c->comm) return eng_fail(c->e[0], RL_E_INVALID, single);
+  return eng_override_rules_enable(c->e[0], cfg);
+}
+
+int rl_override_rules_info_get(rl_ctx* c, rl_override_rules_info* info) {
+  if (!c) return fail(c, RL_E_INVALID, "gpu: null ctx");
+  if (c->n > 1) return fail(c, RL_E_INVALID, "gpu: override rules are not enabled on this ctx (rl_override_rules_enable)");
+  return eng_override_rules_info_get(c->e[0], info);
+}
+
+int rl_override_rule_keys(rl_ctx* c, uint32_t from_rule, uint32_t n, uint8_t* bytes, uint64_t cap, uint32_t* off,
+                          uint64_t* needed) {
+  if (!c) return fail(c, RL_E_INVALID, "gpu: null ctx");
+  if (c->n > 1) return fail(c, RL_E_INVALID, "gpu: override rules are not enabled on this ctx (rl_override_rules_enable)");
+  return eng_override_rule_keys(c->e[0], from_rule, n, bytes, cap, off, needed);
+}
+
 int rl_debug_respond(rl_ctx* c, uint32_t n_requests, uint32_t n_descriptors, const uint32_t* req_idx,
                      const uint8_t* req_status, const rl_request_result* answers, uint32_t opts,
                      const rl_response_format* fmt, rl_response_batch* resp) {

@@ -80,6 +80,7 @@ struct RequestSlot {
   // for the batch's turn. failed: refused by the middle stage's checks.
   uint32_t stage = 0;
   bool wire = false, failed = false;
+  bool ov = false;               // counted on a ctx with device-interned override rules
   uint8_t* wbuf = nullptr;       // the count stage's arrays (sized by the request count), allocated on first use
   size_t wbuf_cap = 0;
   uint32_t* h_wcnt = nullptr;    // pinned [8]: descriptors, entries, domain bytes, entry bytes, error bits
@@ -202,6 +203,12 @@ struct Engine {
   uint32_t rq_head = 0, rq_n = 0;
   int rq_fail = 0;
   std::string rq_fail_msg;
+  // override stats keys interned on the device (rl_override_rules_enable): the
+  // table k_wire_count reads and k_wire_intern extends, for the ctx's lifetime.
+  // ov_order: the last batch's k_wire_intern (the next one waits for it).
+  bool ov_on = false, ov_ordered = false;
+  OvDev ov{};
+  hipEvent_t ov_order = nullptr;
   // host-fed async batches: NBUF staging slots and two copy streams, so that
   // batch t+1's inputs cross PCIe and batch t-1's outputs come back while
   // batch t's kernels run (allocated on first use)
@@ -299,6 +306,11 @@ int eng_do_limit_wire_async(Engine* c, const rl_wire_batch* in, rl_wire_result* 
 // Every engine entry point but the packed one and eng_batch_progress passes
 // rq_n: the calls of all paths then take effect in submission order.
 int eng_requests_advance(Engine* c, uint32_t must);
+// rl_override_rules_enable / _info_get / rl_override_rule_keys on this engine.
+int eng_override_rules_enable(Engine* c, const rl_override_rules_config* cfg);
+int eng_override_rules_info_get(Engine* c, rl_override_rules_info* info);
+int eng_override_rule_keys(Engine* c, uint32_t from_rule, uint32_t n, uint8_t* bytes, uint64_t cap, uint32_t* off,
+                           uint64_t* needed);
 int eng_debug_verdict(Engine* c, uint32_t n_requests, uint32_t n_descriptors, const uint32_t* req_idx,
                       const uint8_t* match, const uint8_t* code, const uint32_t* limit_remaining,
                       const uint32_t* reset_s, const uint32_t* requests_per_unit, uint32_t opts,

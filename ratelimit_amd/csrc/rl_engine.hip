@@ -623,6 +623,9 @@ void eng_destroy(Engine* c) {
   }
   if (c->route_ready) (void)hipEventDestroy(c->route_ready);
   if (c->caller_ready) (void)hipEventDestroy(c->caller_ready);
+  if (c->ov_order) (void)hipEventDestroy(c->ov_order);
+  for (void* p : {(void*)c->ov.slots, (void*)c->ov.koff, (void*)c->ov.klen, (void*)c->ov.arena, (void*)c->ov.ctr})
+    if (p) (void)hipFree(p);
   if (c->h_base) (void)hipHostFree(c->h_base);
   const Scratch& s0 = c->s[0];
   void* bufs[] = {c->slots, c->log, c->log_ctr, c->tear, c->arena, c->arena2, c->errw, s0.stripes, s0.time_floor, s0.counters, c->d_stem, c->d_off,
@@ -2099,6 +2102,9 @@ int request_middle(Engine* c, RequestSlot& s) {
                o_kind = piece(n * 4ull), o_rpu = piece(n * 4ull), o_rule = piece(n * 4ull), o_cnt = piece(16),
                o_code = piece(n), o_rem = piece(n * 4ull), o_reset = piece(n * 4ull), o_match = piece(n),
                o_orule = piece(n * 4ull), o_orpu = piece(n * 4ull), o_ounit = piece(n), o_tmp = piece(scan);
+  // the dense override arrays, as the packed path lays them out: only for a batch that carries overrides
+  const bool has_ov = s.ov && s.h_wcnt[5] && n;
+  const size_t o_ov = has_ov ? piece(n * 10ull) : 0;
   const bool has_v = s.has_verdict || s.has_resp;
   const size_t o_verdict = has_v ? piece(verdict_layout(nq).bytes) : 0;
   s.o_resp = s.has_resp && nq ? piece(resp_layout(nq, n, s.resp_bound).total) : 0;
@@ -2127,8 +2133,13 @@ int request_middle(Engine* c, RequestSlot& s) {
   wo.dom = M + o_dom;
   wo.desc = M + o_desc;
   wo.err = m.count + 2;
+  wo.ov_rpu = has_ov ? (uint32_t*)(M + o_ov) : nullptr;
+  wo.ov_rule = has_ov ? wo.ov_rpu + n : nullptr;
+  wo.ovf = has_ov ? (uint8_t*)(wo.ov_rule + n) : nullptr;
+  wo.ov_unit = has_ov ? wo.ovf + n : nullptr;
+  if (has_ov) HIPCHK(c, hipMemsetAsync(M + o_ov, 0, n * 10ull, st));
   if (!nq) HIPCHK(c, hipMemsetAsync(wo.dom_off, 0, 4, st));
-  launch_wire_emit(s.w, wo, st);
+  launch_wire_emit(s.w, wo, st, has_ov ? &c->ov : nullptr);
   ReqDev r;
   r.n_req = nq;
   r.n_desc = n;
@@ -2144,10 +2155,10 @@ int request_middle(Engine* c, RequestSlot& s) {
   r.desc = wo.desc;
   r.klen = wo.klen;
   r.vlen = wo.vlen;
-  r.ovf = nullptr;
-  r.ov_rpu = nullptr;
-  r.ov_unit = nullptr;
-  r.ov_rule = nullptr;
+  r.ovf = wo.ovf;
+  r.ov_rpu = wo.ov_rpu;
+  r.ov_unit = wo.ov_unit;
+  r.ov_rule = wo.ov_rule;
   PackOut po{h.stem, h.off, h.req, h.unit, h.flags, h.limit, h.hits, h.rule, g.max_stem_bytes};
   launch_match(c->cfg_dev, r, m, po, M + o_tmp, scan, st);
   HIPCHK(c, hipGetLastError());
@@ -2317,7 +2328,7 @@ int eng_do_limit_requests_packed_async(Engine* c, const rl_request_batch_packed*
   s.has_out = out != nullptr;
   s.has_verdict = verdict != nullptr;
   s.stage = 0;
-  s.wire = s.failed = s.has_resp = false;
+  s.wire = s.failed = s.has_resp = s.ov = false;
   if (out) s.out = *out;
   if (verdict) s.verdict = *verdict;
   if (verdict && !nq && verdict->global_shadow) *verdict->global_shadow = 0;
@@ -2387,7 +2398,8 @@ int eng_do_limit_wire_async(Engine* c, const rl_wire_batch* in, rl_wire_result* 
     return o;
   };
   const size_t o_reqw = piece(nq * 16ull), o_tsum = piece(T * 16ull), o_index = piece((T + 1) * 16ull),
-               o_cnt = piece(32), o_status = piece(nq), o_first = piece((nq + 1) * 4ull);
+               o_cnt = piece(32), o_status = piece(nq), o_first = piece((nq + 1) * 4ull),
+               o_miss = c->ov_on ? piece(nq * 4ull) : 0;
   if (need > s.wbuf_cap || B > h.cbuf_cap) HIPCHK(c, hipStreamSynchronize(st));  // the slot's previous batch
   if (need > s.wbuf_cap) {
     if (s.wbuf) HIPCHK(c, hipFree(s.wbuf));
@@ -2426,8 +2438,11 @@ int eng_do_limit_wire_async(Engine* c, const rl_wire_batch* in, rl_wire_result* 
   w.cnt = (uint32_t*)(W + o_cnt);
   w.status = W + o_status;
   w.desc_first = (uint32_t*)(W + o_first);
+  w.n_rules = in->n_rules;
+  w.miss = c->ov_on ? (uint32_t*)(W + o_miss) : nullptr;
   HIPCHK(c, hipMemsetAsync(w.cnt, 0, 32, st));
-  launch_wire_count(w, st);
+  launch_wire_count(w, st, c->ov_on ? &c->ov : nullptr, c->ov_order, c->ov_ordered);
+  if (c->ov_on && T) c->ov_ordered = true;
   HIPCHK(c, hipGetLastError());
   ToHost th{};
   th.src[0] = (const uint8_t*)w.cnt;
@@ -2439,6 +2454,7 @@ int eng_do_limit_wire_async(Engine* c, const rl_wire_batch* in, rl_wire_result* 
   s.stage = 1;
   s.wire = true;
   s.failed = false;
+  s.ov = c->ov_on;
   s.w = w;
   s.wres = *wire;
   s.n = 0;
@@ -2459,6 +2475,117 @@ int eng_do_limit_wire_async(Engine* c, const rl_wire_batch* in, rl_wire_result* 
     if (!nq) resp->resp_off[0] = 0;
   }
   c->rq_n++;
+  return RL_OK;
+}
+
+// ---- override stats keys interned on the device (rl_override_rules_enable) --
+
+int eng_override_rules_enable(Engine* c, const rl_override_rules_config* cfg) {
+  if (!c || !cfg) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (c->ov_on) return set_err(c, RL_E_INVALID, "gpu: rl_override_rules_enable: already enabled on this ctx");
+  if (cfg->reserved[0] || cfg->reserved[1] || cfg->reserved[2] || cfg->reserved[3])
+    return set_err(c, RL_E_INVALID, "gpu: rl_override_rules_config: reserved field not zero");
+  if (!cfg->capacity || (uint64_t)cfg->first_rule + cfg->capacity > c->cfg.max_rules)
+    return set_err(c, RL_E_INVALID, "gpu: rl_override_rules_config: capacity zero or first_rule + capacity > max_rules");
+  RQ_SETTLE(c);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  // (offsets into the arena are 32-bit: it holds at most 4 GiB - 1)
+  const uint64_t want = cfg->key_bytes ? cfg->key_bytes : 64ull * cfg->capacity;
+  const uint32_t arena_cap = (uint32_t)std::min<uint64_t>(want, 0xFFFFFFFFull);
+  uint64_t nslots = 64;
+  while (nslots < 4ull * cfg->capacity) nslots *= 2;  // (a quarter full at the most: short probes)
+  OvDev t{};
+  hipEvent_t ev = nullptr;
+  const bool ok = dalloc(&t.slots, nslots) == hipSuccess && dalloc(&t.koff, cfg->capacity) == hipSuccess &&
+                  dalloc(&t.klen, cfg->capacity) == hipSuccess && dalloc(&t.arena, arena_cap) == hipSuccess &&
+                  dalloc(&t.ctr, 2) == hipSuccess &&
+                  hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess &&
+                  hipMemsetAsync(t.slots, 0, nslots * 8, c->stream) == hipSuccess &&
+                  hipMemsetAsync(t.ctr, 0, 16, c->stream) == hipSuccess &&
+                  hipStreamSynchronize(c->stream) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    for (void* p : {(void*)t.slots, (void*)t.koff, (void*)t.klen, (void*)t.arena, (void*)t.ctr})
+      if (p) (void)hipFree(p);
+    if (ev) (void)hipEventDestroy(ev);
+    return set_err(c, RL_E_HIP, "gpu: rl_override_rules_enable: device allocation failed");
+  }
+  t.mask = (uint32_t)(nslots - 1);
+  t.first_rule = cfg->first_rule;
+  t.capacity = cfg->capacity;
+  t.arena_cap = arena_cap;
+  t.k0 = c->hk.k0;
+  t.k1 = c->hk.k1;
+  c->ov = t;
+  c->ov_order = ev;
+  c->ov_on = true;
+  return RL_OK;
+}
+
+namespace {
+// The table's counter words, after every submitted batch.
+int ov_counters(Engine* c, unsigned long long* ctr) {
+  RQ_SETTLE(c);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream;
+  HIPCHK(c, after_batches(c, st));
+  if (c->ov_ordered) HIPCHK(c, hipStreamWaitEvent(st, c->ov_order, 0));
+  HIPCHK(c, hipMemcpyAsync(ctr, c->ov.ctr, 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return RL_OK;
+}
+}  // namespace
+
+int eng_override_rules_info_get(Engine* c, rl_override_rules_info* info) {
+  if (!c || !info) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (!c->ov_on) return set_err(c, RL_E_INVALID, "gpu: override rules are not enabled on this ctx (rl_override_rules_enable)");
+  unsigned long long ctr[2];
+  if (const int rc = ov_counters(c, ctr)) return rc;
+  rl_override_rules_info x{};
+  x.first_rule = c->ov.first_rule;
+  x.capacity = c->ov.capacity;
+  x.rules = (uint32_t)(ctr[0] >> 32);
+  x.key_bytes_used = (uint32_t)ctr[0];
+  x.key_bytes_cap = c->ov.arena_cap;
+  x.deferred_full = ctr[1];
+  *info = x;
+  return RL_OK;
+}
+
+int eng_override_rule_keys(Engine* c, uint32_t from_rule, uint32_t n, uint8_t* bytes, uint64_t cap, uint32_t* off,
+                           uint64_t* needed) {
+  if (!c || !off) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (!c->ov_on) return set_err(c, RL_E_INVALID, "gpu: override rules are not enabled on this ctx (rl_override_rules_enable)");
+  unsigned long long ctr[2];
+  if (const int rc = ov_counters(c, ctr)) return rc;
+  const uint32_t rules = (uint32_t)(ctr[0] >> 32), first = c->ov.first_rule;
+  if (from_rule < first || from_rule - first > rules || n > rules - (from_rule - first))
+    return set_err(c, RL_E_INVALID, "gpu: rl_override_rule_keys: range outside the ids handed out");
+  off[0] = 0;
+  if (needed) *needed = 0;
+  if (!n) return RL_OK;
+  const uint32_t i0 = from_rule - first;
+  std::vector<uint32_t> koff(n), klen(n);
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(koff.data(), c->ov.koff + i0, n * 4ull, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(klen.data(), c->ov.klen + i0, n * 4ull, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    if (koff[i] > c->ov.arena_cap || klen[i] > c->ov.arena_cap - koff[i])
+      return set_err(c, RL_E_HIP, "gpu: rl_override_rule_keys: a key lies outside the arena");
+    total += klen[i];
+    off[i + 1] = (uint32_t)total;
+  }
+  if (needed) *needed = total;
+  if (total > cap || total > 0xFFFFFFFFull || (total && !bytes))
+    return set_err(c, RL_E_CAPACITY, "gpu: rl_override_rule_keys: the keys take " + std::to_string(total) + " bytes");
+  // (ids are handed out with their bytes, in one step: consecutive ids lie next to each other unless
+  // inserts raced; copied key by key all the same, the call is rare)
+  for (uint32_t i = 0; i < n; i++)
+    if (klen[i])
+      HIPCHK(c, hipMemcpyAsync(bytes + off[i], c->ov.arena + koff[i], klen[i], hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
   return RL_OK;
 }
 

@@ -178,6 +178,34 @@ constexpr uint32_t MATCH_ERR_WIRE = 8;  // k_wire_emit: a message's re-walk left
 constexpr uint32_t WIRE_ERR_OFF = 1;    // msg_off decreasing or past msgs_bytes
 constexpr uint32_t WIRE_ERR_SUM = 2;    // a batch total does not fit 32 bits
 
+// The override stats keys interned on the device (rl_override_rules_enable):
+// descriptorKey bytes -> a dense index (rule id - first_rule). Open addressing
+// over `slots`: 0 empty, else tag (the hash's high word) << 32 | low word, the
+// low word being index + 1 once published, OV_BUSY while its one inserter
+// (k_wire_intern) writes the key, OV_DEAD for a slot whose insert found no id
+// or arena space (never reused: probes pass it). A key's bytes, offset and
+// length are written once, before the slot word is published (agent-scope
+// release); readers match only published words (acquire) and confirm the full
+// bytes. Probes are bounded by OV_PROBE.
+constexpr uint32_t OV_BUSY = 0xFFFFFFFFu, OV_DEAD = 0xFFFFFFFEu, OV_NONE = 0xFFFFFFFFu;
+constexpr uint32_t OV_PROBE = 64, OV_KEY_MAX = 65535u;
+// Every override's key repeats the message's domain, so a long domain in front of many small overrides
+// makes a lane hash far more bytes than the message holds. A message whose overrides x (domain bytes + 1)
+// exceed OV_WORK_X times its own length stays deferred: a lane's work is linear in its payload.
+constexpr uint32_t OV_WORK_X = 16;
+struct OvDev {
+  unsigned long long* slots;  // [mask + 1]
+  uint32_t mask;
+  uint32_t first_rule, capacity;
+  uint32_t arena_cap;         // bytes behind arena (< 2^32)
+  uint32_t* koff;             // [capacity] a key's first byte in arena
+  uint32_t* klen;             // [capacity]
+  uint8_t* arena;
+  // [0] ids handed out << 32 | arena bytes used (one word: both or neither are taken), [1] deferred_full
+  unsigned long long* ctr;
+  uint64_t k0, k1;            // the ctx's hash key
+};
+
 // A wire batch on the device: the sections of the copied buffer and the
 // count stage's arrays (sized by the request count alone).
 struct WireDev {
@@ -191,9 +219,14 @@ struct WireDev {
   uint32_t* cnt;   // [8] the totals {descriptors, entries, domain bytes, entry bytes}, error bits
   uint8_t* status;        // [n_req] rl_wire_status
   uint32_t* desc_first;   // [n_req + 1]
+  // enabled ctxs only (cnt[5]: messages that stayed OK with an override, cnt[6]: entries of miss)
+  uint32_t n_rules;       // override rule ids must stay below it
+  uint32_t* miss;         // [n_req] messages with an override key the count stage did not find
 };
 
-// What k_wire_emit writes: ReqDev's arrays (all but the overrides) and the clocks.
+// What k_wire_emit writes: ReqDev's arrays and the clocks. The dense override
+// arrays (null unless the batch carries overrides; zeroed on the stream) are
+// written for the descriptors with `limit` alone.
 struct WireOut {
   uint4 tot;  // the count stage's totals, capacity-checked on the host
   uint32_t* dom_off;
@@ -207,11 +240,21 @@ struct WireOut {
   uint8_t* dom;
   uint8_t* desc;
   uint32_t* err;  // MatchBuf::count + 2
+  uint8_t* ovf;
+  uint32_t* ov_rpu;
+  uint8_t* ov_unit;
+  uint32_t* ov_rule;
 };
 
 // k_wire_count per tile, then the scan over the tiles (index, totals, desc_first[n_req]).
-void launch_wire_count(const WireDev& w, hipStream_t st);
-void launch_wire_emit(const WireDev& w, const WireOut& o, hipStream_t st);
+// ov (enabled ctxs): messages with `limit` are looked up in the intern table
+// by the count kernel; k_wire_intern (one workgroup; the caller orders it after
+// the previous batch's by `ov_order`, recorded again behind it) inserts the
+// keys it missed and defers what it cannot serve, before the scan.
+void launch_wire_count(const WireDev& w, hipStream_t st, const OvDev* ov = nullptr, hipEvent_t ov_order = nullptr,
+                       bool ov_wait = false);
+// ov: the batch carries overrides (o.ovf and its kin are set).
+void launch_wire_emit(const WireDev& w, const WireOut& o, hipStream_t st, const OvDev* ov = nullptr);
 // overall_code[q] = 0 where status[q] != RL_WIRE_OK
 void launch_wire_code(const uint8_t* status, uint8_t* o_code, uint32_t n_req, hipStream_t st);
 

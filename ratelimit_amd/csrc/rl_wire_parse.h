@@ -12,7 +12,17 @@
 // The walk reports to a sink S:
 //   s.entry(b, key_pos, key_len, value_pos, value_len)   one Entry, in order
 //   s.descriptor(entries)                               one RateLimitDescriptor ended
+//   s.limit(b, ordinal, rpu, unit, desc_pos, desc_end)  (optional member) a descriptor with `limit`
 // A sink bounds its own stores; the walk never stores.
+//
+// Overrides: walk_message<B, S, true> (the default) defers every message that
+// carries a descriptor with `limit`, as before. walk_message<B, S, false>
+// parses the override as rl_pack.cpp's parse_descriptor does (the last written
+// requests_per_unit and unit win across repeated `limit` fields, rpu truncated
+// to 32 bits, unit clamped to 255) and reports it to the sink's limit() member,
+// if it has one, when the descriptor ends: its ordinal in the message and the
+// descriptor's own bytes [desc_pos, desc_end), from which descriptor_key()
+// streams descriptorKey(domain, descriptor) once the message's domain is known.
 #pragma once
 
 #include <stdint.h>
@@ -86,11 +96,24 @@ RLW_HD bool walk_entry(Rd<B> r, S& s) {
   return true;
 }
 
-// RateLimitDescriptor: 1 entries, 2 limit (RateLimitOverride: 1, 2 varints).
-// False: malformed. *defer is set for an override or more than ITEM_MAX entries.
+// s.limit(...) where S has such a member; nothing otherwise.
 template <class B, class S>
-RLW_HD bool walk_descriptor(Rd<B> r, S& s, bool* defer) {
+RLW_HD auto report_limit(S& s, const B& b, uint32_t ord, uint32_t rpu, uint32_t unit, uint32_t p, uint32_t e, int)
+    -> decltype(s.limit(b, ord, rpu, unit, p, e), void()) {
+  s.limit(b, ord, rpu, unit, p, e);
+}
+template <class B, class S>
+RLW_HD void report_limit(S&, const B&, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, long) {}
+
+// RateLimitDescriptor: 1 entries, 2 limit (RateLimitOverride: 1, 2 varints).
+// False: malformed. *defer is set for more than ITEM_MAX entries and, with
+// DEFER_OV, for an override; without it the override is reported to the sink.
+template <bool DEFER_OV, class B, class S>
+RLW_HD bool walk_descriptor(Rd<B> r, S& s, bool* defer, uint32_t ord) {
   uint32_t ne = 0;
+  const uint32_t p0 = r.p;
+  bool has_limit = false;
+  uint32_t rpu = 0, unit = 0;
   while (r.more()) {
     const uint64_t tag = r.varint();
     if (!field_ok(tag)) return false;
@@ -102,13 +125,21 @@ RLW_HD bool walk_descriptor(Rd<B> r, S& s, bool* defer) {
     } else if (f == 2 && wt == 2) {
       Rd<B> o = r.sub();
       if (!r.ok) return false;
-      *defer = true;
+      if (DEFER_OV) *defer = true;
+      else has_limit = true;
       while (o.more()) {
         const uint64_t t2 = o.varint();
         if (!field_ok(t2)) return false;
         const uint32_t f2 = (uint32_t)(t2 >> 3), w2 = (uint32_t)(t2 & 7u);
-        if ((f2 == 1 || f2 == 2) && w2 == 0) (void)o.varint();
-        else o.skip(w2);
+        if ((f2 == 1 || f2 == 2) && w2 == 0) {
+          const uint32_t v = (uint32_t)o.varint();
+          if (!DEFER_OV) {
+            if (f2 == 1) rpu = v;
+            else unit = v;
+          }
+        } else {
+          o.skip(w2);
+        }
       }
       if (!o.ok) return false;
     } else {
@@ -118,6 +149,7 @@ RLW_HD bool walk_descriptor(Rd<B> r, S& s, bool* defer) {
   if (!r.ok) return false;
   if (ne > ITEM_MAX) *defer = true;
   s.descriptor(ne);
+  if (!DEFER_OV && has_limit) report_limit(s, r.b, ord, rpu, unit > 255u ? 255u : unit, p0, r.e, 0);
   return true;
 }
 
@@ -129,7 +161,7 @@ struct Message {
 };
 
 // RateLimitRequest at [p, e): 1 domain, 2 descriptors, 3 hits_addend.
-template <class B, class S>
+template <class B, class S, bool DEFER_OV = true>
 RLW_HD Message walk_message(B b, uint32_t p, uint32_t e, S& s) {
   Rd<B> r{b, p, e, true};
   Message m{ST_OK, 0, p, 0, 0};
@@ -140,7 +172,7 @@ RLW_HD Message walk_message(B b, uint32_t p, uint32_t e, S& s) {
     const uint32_t f = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7u);
     if (f == 2 && wt == 2) {
       const Rd<B> x = r.sub();
-      if (!r.ok || !walk_descriptor(x, s, &defer)) { r.ok = false; break; }
+      if (!r.ok || !walk_descriptor<DEFER_OV>(x, s, &defer, m.n_desc)) { r.ok = false; break; }
       m.n_desc++;
     } else if (f == 1 && wt == 2) {
       const Rd<B> x = r.sub();
@@ -166,6 +198,60 @@ struct CountSink {
     ent_bytes += kl + vl + 2u;
   }
   RLW_HD void descriptor(uint32_t) {}
+};
+
+// descriptorKey(domain, descriptor) (config_impl.go:300-312) of the descriptor
+// whose bytes are [p, e) of a message the walk accepted, streamed to f:
+//   f.bytes(b, pos, len)   len bytes of the source from pos
+//   f.sep(c)               one separator byte
+// domain '.' then per entry, joined by '.': key, and '_' value when the value
+// is not empty (so ("a_b", "") and ("a", "b") are one key). The last key and
+// value of an entry win, as in walk_entry. Nothing is staged: a functor that
+// only adds lengths costs no byte read.
+template <class B, class F>
+RLW_HD void descriptor_key(const B& b, uint32_t dom_pos, uint32_t dom_len, uint32_t p, uint32_t e, F& f) {
+  f.bytes(b, dom_pos, dom_len);
+  f.sep('.');
+  Rd<B> r{b, p, e, true};
+  bool first = true;
+  while (r.more()) {
+    const uint64_t tag = r.varint();
+    const uint32_t fn = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7u);
+    if (fn == 1 && wt == 2) {
+      Rd<B> x = r.sub();
+      if (!r.ok) return;
+      uint32_t kp = 0, kl = 0, vp = 0, vl = 0;
+      while (x.more()) {
+        const uint64_t t2 = x.varint();
+        const uint32_t f2 = (uint32_t)(t2 >> 3), w2 = (uint32_t)(t2 & 7u);
+        if ((f2 == 1 || f2 == 2) && w2 == 2) {
+          const Rd<B> y = x.sub();
+          if (f2 == 1) { kp = y.p; kl = y.e - y.p; }
+          else { vp = y.p; vl = y.e - y.p; }
+        } else {
+          x.skip(w2);
+        }
+      }
+      if (!x.ok) return;
+      if (!first) f.sep('.');
+      first = false;
+      f.bytes(b, kp, kl);
+      if (vl) {
+        f.sep('_');
+        f.bytes(b, vp, vl);
+      }
+    } else {
+      r.skip(wt);
+    }
+  }
+}
+
+// descriptor_key's length alone.
+struct KeyLen {
+  uint64_t n = 0;
+  template <class B>
+  RLW_HD void bytes(const B&, uint32_t, uint32_t len) { n += len; }
+  RLW_HD void sep(uint8_t) { n++; }
 };
 
 }  // namespace rlwire

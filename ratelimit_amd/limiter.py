@@ -426,6 +426,44 @@ class Backend:
                                                    C.byref(v) if v is not None else None))
         return wr, r, v
 
+    def enable_override_rules(self, first_rule: int, capacity: int, key_bytes: int = 0) -> None:
+        """rl_override_rules_enable: from now on the wire paths answer messages
+        whose descriptors carry a ``limit`` override on the device, their stats
+        keys interned there to the rule ids first_rule, first_rule + 1, ...
+        (at most ``capacity`` of them; ``key_bytes``: room for their bytes, 0 =
+        64 per key). Once per Backend."""
+        cfg = abi.RlOverrideRulesConfig()
+        cfg.first_rule, cfg.capacity, cfg.key_bytes = int(first_rule), int(capacity), int(key_bytes)
+        self._check(self.L.rl_override_rules_enable(self.ctx, C.byref(cfg)))
+
+    def override_rules_info(self) -> dict:
+        """rl_override_rules_info_get, after every submitted batch."""
+        info = abi.RlOverrideRulesInfo()
+        self._check(self.L.rl_override_rules_info_get(self.ctx, C.byref(info)))
+        return {f: int(getattr(info, f)) for f, _ in info._fields_ if f != "reserved"}
+
+    def override_rule_keys(self, from_rule: Optional[int] = None, n: Optional[int] = None) -> List[bytes]:
+        """rl_override_rule_keys: the stats keys (bytes) of the override rule
+        ids [from_rule, from_rule + n); by default all that were handed out."""
+        if from_rule is None or n is None:
+            info = self.override_rules_info()
+            if from_rule is None:
+                from_rule = info["first_rule"]
+            if n is None:
+                n = info["first_rule"] + info["rules"] - from_rule
+        off = np.zeros(n + 1, np.uint32)
+        need = C.c_uint64(0)
+        rc = self.L.rl_override_rule_keys(self.ctx, from_rule, n, None, 0, abi.ptr(off), C.byref(need))
+        if rc == abi.RL_OK:  # (no bytes at all)
+            return [b""] * n
+        if rc != abi.RL_E_CAPACITY:
+            self._check(rc)
+        buf = np.zeros(max(need.value, 1), np.uint8)
+        self._check(self.L.rl_override_rule_keys(self.ctx, from_rule, n, abi.ptr(buf), need.value, abi.ptr(off),
+                                                 C.byref(need)))
+        raw = buf.tobytes()
+        return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+
     @staticmethod
     def response_bound(n_requests: int, n_descriptors: int, header_keys=None) -> int:
         """rl_response_bound: no batch of that shape serializes to more bytes."""
@@ -981,7 +1019,7 @@ class GpuRateLimitService:
 
     def __init__(self, config_files, near_limit_ratio: float = 0.8, local_cache: bool = False,
                  cache_key_prefix: str = "", per_second: bool = False, global_shadow_mode: bool = False,
-                 header_keys=None, **backend_kw):
+                 header_keys=None, device_overrides: bool = False, override_capacity: int = 256, **backend_kw):
         from .config import ConfigTree
         self.interner = RuleInterner()
         self.tree = ConfigTree.from_yaml(config_files, cache_key_prefix, self.interner)
@@ -992,6 +1030,19 @@ class GpuRateLimitService:
             k.encode() if isinstance(k, str) else bytes(k) for k in header_keys)
         self.backend = Backend(near_limit_ratio, local_cache, per_second, **backend_kw)
         self.backend.load_config(self.tree)
+        # device_overrides: the payload paths answer messages with a ``limit`` override on the device
+        # (rl_override_rules_enable); their stats keys take the rule ids after the config's, at most
+        # override_capacity of them, and their names are fetched when a batch's stats first show a new id
+        self.device_overrides = bool(device_overrides)
+        self._ov_first = len(self.interner.keys)
+        self._ov_capacity = int(override_capacity)
+        self._ov_names = []
+        if self.device_overrides:
+            try:
+                self.backend.enable_override_rules(self._ov_first, self._ov_capacity)
+            except Exception:
+                self.backend.close()
+                raise
         self.stats = {}  # stats key -> [6 counters] (the gostats store)
         self.global_shadow_count = 0  # stats.GlobalShadowMode (should_rate_limit_verdicts)
 
@@ -1005,6 +1056,24 @@ class GpuRateLimitService:
             row = self.stats.setdefault(keys[i], [0] * abi.RL_NUM_STATS)
             for j in range(abi.RL_NUM_STATS):
                 row[j] += int(st[i, j])
+
+    def _wire_rules(self) -> int:
+        """n_rules of a payload batch: the config's rule ids, and the device-interned override ids."""
+        if self.device_overrides:
+            return self._ov_first + self._ov_capacity
+        return max(len(self.interner.keys), 1)
+
+    def _wire_keys(self, stats):
+        """The stats keys by rule id for a payload batch's stats rows: the
+        config's, then the device-interned override keys, fetched only when a
+        non-zero row lies beyond the names already held."""
+        if not self.device_overrides:
+            return None
+        rows = np.nonzero(stats.reshape(-1, abi.RL_NUM_STATS).any(axis=1))[0]
+        if len(rows) and int(rows[-1]) >= self._ov_first + len(self._ov_names):
+            got = self.backend.override_rule_keys(self._ov_first + len(self._ov_names))
+            self._ov_names += [k.decode(errors="surrogateescape") for k in got]
+        return self.interner.keys[:self._ov_first] + self._ov_names
 
     def should_rate_limit_verdicts(self, requests, nows, per_descriptor: bool = True):
         """-> ([RequestVerdict] per request in arrival order, this call's
@@ -1075,7 +1144,8 @@ class GpuRateLimitService:
         RateLimitRequest messages as the gRPC server received them. Every batch
         goes through ``rl_do_limit_wire_async`` unparsed, without waiting, then
         one synchronize(). The messages the device deferred (a descriptor with
-        a ``limit`` override, or past the packed layout's per-item limits) are
+        a ``limit`` override unless the service was made with
+        ``device_overrides``, or past the packed layout's per-item limits) are
         then resubmitted through ``RequestPacker`` and the packed path, batch by
         batch: they take effect after every batch of this call, in batch order.
         -> per batch what should_rate_limit_verdicts returns, a malformed
@@ -1086,7 +1156,7 @@ class GpuRateLimitService:
         arena = PinnedArena()
         packer = None
         try:
-            n_rules = max(len(self.interner.keys), 1)
+            n_rules = self._wire_rules()
             max_batch = int(self.backend.cfg.max_batch)
             flight = []
             for msgs, nows in batches:
@@ -1114,7 +1184,7 @@ class GpuRateLimitService:
                 res.update({k: a[:nq] for k, a in ver.items() if k != "global_shadow"})
                 res["global_shadow"] = int(ver["global_shadow"][0])
                 first = wire["desc_first"][:nq + 1]
-                vs, shadow = self._verdicts(first[1:] - first[:-1], res, per_descriptor)
+                vs, shadow = self._verdicts(first[1:] - first[:-1], res, per_descriptor, self._wire_keys(res["stats"]))
                 status = wire["req_status"][:nq]
                 for q in np.nonzero(status == abi.RL_WIRE_MALFORMED)[0]:
                     vs[q] = RedisError("gpu: malformed RateLimitRequest", abi.RL_E_INVALID)
@@ -1162,7 +1232,7 @@ class GpuRateLimitService:
         packer = None
         hk = self.header_keys
         try:
-            n_rules = max(len(self.interner.keys), 1)
+            n_rules = self._wire_rules()
             max_batch = int(self.backend.cfg.max_batch)
             flight = []
             for msgs, nows in batches:
@@ -1183,7 +1253,8 @@ class GpuRateLimitService:
             again = []  # (batch, its deferred messages' indices)
             for b, (wb, wire, out, ver, resp, _) in enumerate(flight):
                 nq = wb.n_requests
-                self._add_stats(out["stats"][:n_rules * abi.RL_NUM_STATS])
+                st = out["stats"][:n_rules * abi.RL_NUM_STATS]
+                self._add_stats(st, self._wire_keys(st))
                 shadow = int(ver["global_shadow"][0])
                 self.global_shadow_count += shadow
                 off = resp["resp_off"][:nq + 1]

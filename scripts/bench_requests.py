@@ -41,9 +41,23 @@ the requests per thread): it is what the device spares the host.
 --respond-headers is --respond with the three RateLimit-* header names
 configured, so that every response also carries its three HeaderValues.
 
+--override-share P (with --path wire-async --from-payloads) gives a share P of
+the requests a ``limit`` override on their first descriptor (requests_per_unit
+1000, SECOND); their tenants are folded onto OVERRIDE_TENANTS values, so the
+set of override stats keys is small and stable, as a fleet's per-route
+overrides are. Without --device-overrides the device defers those messages and
+the host answers them as a service does today: when a buffer's batch is
+complete, its deferred messages go through rl_packer_pack and the synchronous
+rl_do_limit_requests, inside the timed loop. With --device-overrides the ctx
+interns the override stats keys on the GPU (rl_override_rules_enable) and the
+timed loop is the plain wire loop; the warm-up checks that nothing is deferred.
+The rate counts every descriptor of every request either way. The parity check
+against the packed DoLimit path is skipped (the overrides change the limits).
+
     python scripts/bench_requests.py [--config c1|c2] [--steps K] [--verdict off|full|only]
                                      [--path sync|packed-async|wire-async] [--respond | --respond-headers]
                                      [--from-payloads [--pack-threads N]]
+                                     [--override-share P [--device-overrides]]
 """
 import argparse
 import ctypes as C
@@ -62,6 +76,32 @@ from ratelimit_amd.limiter import Backend, PinnedArena  # noqa: E402
 
 PACKED_RING = 8  # packed buffers (and output sets) in rotation on --path packed-async
 HEADER_KEYS = (b"RateLimit-Limit", b"RateLimit-Remaining", b"RateLimit-Reset")  # --respond-headers
+OVERRIDE_TENANTS = 1024   # --override-share: distinct tenants (override stats keys) among the override requests
+OVERRIDE_CAPACITY = 4096  # --device-overrides: rl_override_rules_config.capacity
+OVERRIDE_LIMIT = bytes([0x12, 0x05, 0x08, 0xE8, 0x07, 0x10, 0x01])  # limit {requests_per_unit: 1000, unit: SECOND}
+
+
+def override_payloads(rows, tenants, share, rng):
+    """c1_payloads' rows with a share of the requests carrying OVERRIDE_LIMIT on their first descriptor
+    -> (the payload bytes, uint32 offsets [nq + 1], the override requests' indices)."""
+    nq, L = rows.shape
+    mask = rng.random(nq) < share
+    idx = np.nonzero(mask)[0]
+    ov = W.c1_payloads(np.asarray(tenants)[idx] % OVERRIDE_TENANTS, rows[idx, -1])
+    d0 = 2 + rows[0, 1]  # the first descriptor: tag, length, body (after the domain field)
+    assert rows[0, d0] == 0x12 and rows[0, d0 + 1] + len(OVERRIDE_LIMIT) < 128
+    end = d0 + 2 + rows[0, d0 + 1]
+    lim = np.tile(np.frombuffer(OVERRIDE_LIMIT, np.uint8), (len(idx), 1))
+    ov = np.concatenate([ov[:, :end], lim, ov[:, end:]], axis=1)
+    ov[:, d0 + 1] += len(OVERRIDE_LIMIT)
+    lens = np.where(mask, ov.shape[1], L).astype(np.uint64)
+    off = np.zeros(nq + 1, np.uint64)
+    np.cumsum(lens, out=off[1:])
+    flat = np.empty(int(off[-1]), np.uint8)
+    plain = np.nonzero(~mask)[0]
+    flat[(off[plain][:, None] + np.arange(L, dtype=np.uint64)).reshape(-1)] = rows[plain].reshape(-1)
+    flat[(off[idx][:, None] + np.arange(ov.shape[1], dtype=np.uint64)).reshape(-1)] = ov.reshape(-1)
+    return flat, off.astype(np.uint32), idx
 
 
 def pinned(a):
@@ -86,6 +126,8 @@ def main():
     ap.add_argument("--pack-threads", type=int, default=1)
     ap.add_argument("--respond", action="store_true")
     ap.add_argument("--respond-headers", action="store_true")
+    ap.add_argument("--override-share", type=float, default=0.0)
+    ap.add_argument("--device-overrides", action="store_true")
     args = ap.parse_args()
     args.respond = args.respond or args.respond_headers
     keys = HEADER_KEYS if args.respond_headers else None
@@ -95,20 +137,33 @@ def main():
         ap.error("--from-payloads goes with --path packed-async or wire-async")
     if not 1 <= args.pack_threads <= 16:
         ap.error("--pack-threads: 1..16")
+    share = args.override_share
+    if (share or args.device_overrides) and not (args.path == "wire-async" and args.from_payloads):
+        ap.error("--override-share / --device-overrides go with --path wire-async --from-payloads")
+    if not 0.0 <= share <= 1.0:
+        ap.error("--override-share: 0..1")
     nq, T = args.requests, args.tenants
     rng = np.random.default_rng(0xC1 if args.config == "c1" else 0xC2)
     zs = W.ZipfSampler(T, 1.1) if args.config == "c2" else None
     kw = dict(table_slots=1 << 26, max_batch=2 * nq, max_rules=16)
+    if share or args.device_overrides:  # (rows for the override stats keys, on either flow)
+        kw["max_rules"] = 2 + OVERRIDE_CAPACITY
     be_req = Backend(0.8, False, **kw)
     be_pk = Backend(0.8, False, **kw)
     tree = ConfigTree.from_yaml([("c1.yaml", W.C1_CONFIG_YAML)])
     be_req.load_config(tree)
-    batches, payloads = [], []
+    wire_rules = 2
+    if args.device_overrides:
+        be_req.enable_override_rules(2, OVERRIDE_CAPACITY)
+        wire_rules = 2 + OVERRIDE_CAPACITY
+    batches, payloads, var = [], [], []
     for b in range(4):
         t = zs.sample(rng, nq) if zs is not None else rng.integers(0, T, nq)
         h = rng.integers(1, 9, nq) if args.config == "c2" else None
         if args.path == "wire-async" or args.from_payloads:
             payloads.append(W.c1_payloads(t, h))  # (pageable: the bytes as the gRPC server received them)
+            if share:
+                var.append(override_payloads(payloads[-1], t, share, rng))
         raw = {k: pinned(v) for k, v in W.c1_requests(t, W.NOW0 + b, h).items()}
         pk, n, _, nr = W.c1_batch(t, W.NOW0 + b, h)
         batches.append((raw, {k: pinned(v) for k, v in pk.items()}, n))
@@ -178,12 +233,18 @@ def main():
     wire_bytes = None
     if args.path == "wire-async":
         for j in range(PACKED_RING):
-            wb = be_req.wire_batch([r.tobytes() for r in payloads[j % 4]], [W.NOW0] * nq, arena, 2)
+            if share:
+                flat, off, _ = var[j % 4]
+                raw = flat.tobytes()
+                msgs = [raw[off[q]:off[q + 1]] for q in range(nq)]
+            else:
+                msgs = [r.tobytes() for r in payloads[j % 4]]
+            wb = be_req.wire_batch(msgs, [W.NOW0] * nq, arena, wire_rules)
             wire_bytes = int(wb.struct.buf_bytes)
             out = None
             if args.verdict != "only":
                 out = {k: arena.array(n, dt) for k, dt in abi.REQUEST_RESULT_DTYPES.items()}
-                out["stats"] = arena.array(2 * abi.RL_NUM_STATS, np.uint64)
+                out["stats"] = arena.array(wire_rules * abi.RL_NUM_STATS, np.uint64)
             ver = None
             if args.verdict != "off":
                 ver = {k: arena.array(nq, dt) for k, dt in abi.REQUEST_VERDICT_DTYPES.items()}
@@ -205,7 +266,10 @@ def main():
 
     def wire_call(j, now, b=None, arrays=False):
         wb, out, ver, now32, wire, off32, body, resp = ring[j]
-        if b is not None:  # --from-payloads: the host's work per batch
+        if b is not None and share:  # --from-payloads: the host's work per batch
+            body[:] = var[b][0]
+            off32[:] = var[b][1]
+        elif b is not None:
             body[:] = payloads[b].reshape(-1)
             off32[:] = msg_off32
         now32[:] = now
@@ -213,6 +277,38 @@ def main():
             return be_req.do_limit_wire_respond_async(wb, wire, out if arrays else {"stats": out["stats"]},
                                                       ver if arrays else None, resp, keys, False, n)
         return be_req.do_limit_wire_async(wb, wire, out, ver, False, n)
+
+    # --override-share without --device-overrides: the deferred messages of ring[j]'s completed batch (batch b's
+    # payloads) through the host packer and the synchronous request path
+    defer_flow = bool(share) and not args.device_overrides
+    rs = {}
+    if defer_flow:
+        m_max = max(len(v[2]) for v in var)
+        ov_len = int(var[0][1][var[0][2][0] + 1] - var[0][1][var[0][2][0]])
+        rs = dict(packer=lib().rl_packer_create(2), rb=abi.RlRequestBatch(), nows=np.zeros(m_max, np.int64),
+                  off=np.arange(m_max + 1, dtype=np.uint64) * ov_len, span=np.arange(ov_len, dtype=np.uint64),
+                  out={k: pinned(np.zeros(2 * m_max, dt)) for k, dt in abi.REQUEST_RESULT_DTYPES.items()})
+        rs["out"]["stats"] = pinned(np.zeros((2 + OVERRIDE_CAPACITY) * abi.RL_NUM_STATS, np.uint64))
+
+    def resubmit(j, b, now):
+        L = lib()
+        status = ring[j][4]["req_status"]
+        idx = np.nonzero(status[:nq] == abi.RL_WIRE_DEFERRED)[0]
+        if not len(idx):
+            return 0
+        flat, off, _ = var[b]
+        body = flat[(off[idx].astype(np.uint64)[:, None] + rs["span"]).reshape(-1)]
+        rs["nows"][:len(idx)] = now
+        rc = L.rl_packer_pack(rs["packer"], abi.ptr(body), abi.ptr(rs["off"]), len(idx), abi.ptr(rs["nows"]),
+                              C.byref(rs["rb"]))
+        assert rc == 0
+        assert rs["rb"].n_rules <= 2 + OVERRIDE_CAPACITY
+        r = abi.RlRequestResult()
+        for k in rs["out"]:
+            setattr(r, k, abi.ptr(rs["out"][k]))
+        rc = L.rl_do_limit_requests(be_req.ctx, C.byref(rs["rb"]), C.byref(r))
+        assert rc == 0, L.rl_last_error(be_req.ctx)
+        return len(idx)
 
     def host_serialize(j, threads, reps=5):
         """rl_response_serialize over ring[j]'s arrays, one contiguous slice of the requests per thread
@@ -344,9 +440,17 @@ def main():
                 ver = {"overall_code": np.concatenate([x["ver"]["overall_code"][:x["m"]] for x in sl])}
         else:
             out, ver = ring[s % PACKED_RING][1:3]
+        if args.path == "wire-async" and defer_flow:  # exactly the override requests are deferred
+            wire = ring[s % PACKED_RING][4]
+            assert np.array_equal(np.nonzero(wire["req_status"][:nq])[0], var[s % 4][2])
+            assert resubmit(s % PACKED_RING, s % 4, W.NOW0 + s) == len(var[s % 4][2])
+            continue
         if args.path == "wire-async":
             wire = ring[s % PACKED_RING][4]
             assert not wire["req_status"].any() and int(wire["n_descriptors"][0]) == n
+        if share:  # (the overrides change the limits: no parity with the packed DoLimit path)
+            assert (out["match"] == abi.RL_MATCH_LIMIT).all() if out is not None else True
+            continue
         if args.respond:  # the device's bytes are the host twin's over the returned arrays
             resp = ring[s % PACKED_RING][7]
             raw, off = be_req.response_serialize(wire["desc_first"][:nq + 1], None, out, ver, keys)
@@ -370,11 +474,14 @@ def main():
     if args.path != "sync":
         base = be_req.batch_progress()[0]
         keep = []
+        resubmitted = 0
         t0 = time.perf_counter()
         for s in range(args.steps):
             # the buffer's previous batch is complete
             while be_req.batch_progress()[1] - base + PACKED_RING * sub_batches <= s * sub_batches:
                 pass
+            if defer_flow and s >= PACKED_RING:  # the buffer's completed batch: its deferred messages, on the host
+                resubmitted += resubmit(s % PACKED_RING, s % 4, W.NOW0 + 8 + s - PACKED_RING)
             if pack_ring:
                 keep.append(packed_from_payloads(s % PACKED_RING, s % 4, W.NOW0 + 8 + s))
             elif args.from_payloads:
@@ -382,6 +489,8 @@ def main():
             else:
                 keep.append(async_call(s % PACKED_RING, W.NOW0 + 8 + s))
         be_req.synchronize()
+        for s in range(max(args.steps - PACKED_RING, 0), args.steps if defer_flow else 0):  # the last batches' deferred
+            resubmitted += resubmit(s % PACKED_RING, s % 4, W.NOW0 + 8 + s)
         res["requests"] = time.perf_counter() - t0
         t0 = time.perf_counter()
         for s in range(args.steps):
@@ -419,6 +528,15 @@ def main():
         out["from_payloads"] = bool(args.from_payloads)
         if pack_ring:
             out["pack_threads"] = NT
+    if share or args.device_overrides:
+        out["override_share"] = share
+        out["device_overrides"] = bool(args.device_overrides)
+        out["override_requests_per_batch"] = [int(len(v[2])) for v in var]
+        out["parity"] = "skipped (overrides change the limits); warm-up checks the statuses"
+        if defer_flow:
+            out["resubmitted_requests"] = resubmitted
+        else:
+            out["override_rules"] = be_req.override_rules_info() if args.device_overrides else None
     if args.respond:
         out["respond"] = True
         out["response_headers"] = bool(args.respond_headers)
