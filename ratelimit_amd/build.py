@@ -18,7 +18,7 @@ SOURCES = ["rl_kernels.hip", "rl_route.hip", "rl_match.hip", "rl_wire.hip", "rl_
            "rl_comm.hip",
            "rl_api.hip",
            "rl_pack.cpp"]
-HEADERS = ["rl_device.h", "rl_kernels.h", "rl_slot_img.h", "rl_hot_select.h", "rl_match.h", "rl_wire_parse.h", "rl_resp_emit.h", "rl_engine.h",
+HEADERS = ["rl_device.h", "rl_kernels.h", "rl_tile.h", "rl_slot_img.h", "rl_hot_select.h", "rl_match.h", "rl_wire_parse.h", "rl_resp_emit.h", "rl_engine.h",
            "rl_comm.h", "rl_transport.h",
            os.path.join("..", "..", "include", "ratelimit_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -328,6 +328,7 @@ Params params(Engine* c, int isolate) {
 
 // Per-batch scratch of one pipeline buffer (sized for max_batch descriptors).
 bool alloc_buffer(Scratch& s, uint32_t n) {
+  static_assert(sizeof(*s.tile) == 8, "Scratch::tile: one 8-byte record per descriptor");
   const size_t items = (size_t)n / (64 * 4 * 8) + 1 + PART_DIGITS;  // BIG_CHUNK-position work items
   bool ok = dalloc(&s.big_meta, PART_DIGITS) == hipSuccess && dalloc(&s.big_n, 1) == hipSuccess &&
             dalloc(&s.big_work, items) == hipSuccess && dalloc(&s.work_n, 1) == hipSuccess &&

@@ -7,13 +7,21 @@
 
 #include "rl_device.h"
 #include "rl_hot_select.h"
+#include "rl_tile.h"
 
 namespace rl {
 
 #ifndef RL_PART_ITEMS
-#define RL_PART_ITEMS 16  // (8: 82 instead of 144 VGPRs, twice the tiles: C1 -3 %, C2 -8 %)
+#define RL_PART_ITEMS 16  // (8, i.e. tiles of 2048 and twice as many of them: C1 -3 %, C2 -8 %)
 #endif
-constexpr uint32_t PART_ITEMS = RL_PART_ITEMS, PART_TILE = 256 * PART_ITEMS;  // k_part: 256 threads x PART_ITEMS
+constexpr uint32_t PART_ITEMS = RL_PART_ITEMS, PART_TILE = 256 * PART_ITEMS;  // k_part's tile: 4096 descriptors
+// k_part spreads a tile over PART_WAVES waves of PART_TILE / (64 x PART_WAVES)
+// items per lane. One tile per CU at C1 (245 tiles): 4 waves x 16 items leave
+// one wave per SIMD and nothing to hide a load or a ballot chain behind
+// (eight waves against four: C1 +1.8 %, profiles/stage_a/).
+constexpr uint32_t PART_WAVES = 8, PART_THREADS = 64 * PART_WAVES;
+constexpr uint32_t PART_WITEMS = PART_TILE / PART_THREADS;  // items per lane
+static_assert(PART_TILE % PART_THREADS == 0, "k_part: whole items per lane");
 constexpr uint32_t PART_BITS = 10, PART_DIGITS = 1u << PART_BITS;   // buckets = top key bits
 #ifndef RL_BIG_BLOCKS
 #define RL_BIG_BLOCKS 64
@@ -28,6 +36,8 @@ struct BigMeta {
   uint32_t heavy[BIG_HEAVY];
 };
 constexpr uint32_t MAX_PART_TILES = 2048 * 16 / PART_ITEMS;  // k_part tiles per batch (max_batch <= 8388608)
+static_assert((uint64_t)MAX_PART_TILES * PART_TILE <= (1ull << TILE_IDX_BITS),
+              "a tile record's index bits hold every descriptor index of the largest batch");
 constexpr uint32_t LONG_RUN = 32;        // runs at least this long take the parallel path
 constexpr uint32_t RUN_SLOW = 1, RUN_FAST = 2, RUN_MULTI = 4;
 // A stem under several units (per-request overrides, config_impl.go:254-265)
@@ -229,7 +239,7 @@ struct Scratch {
   // run segmentation (sorted order)
   uint32_t* hits_s;                    // [n] raw hits, sorted order
   uint32_t* hit_a;                     // [n] raw hits, arrival order (k_prepare)
-  uint4* tile;                         // [n] k_part tile layout: {sort key, index, hits, 0}
+  TileRec* tile;                       // [n] k_part tile layout: {sort key, index | hits9 << 23} (rl_tile.h)
   uint32_t* hit_t;                     // [n] k_bucket large-bucket temp
   uint32_t* segsum;                    // [n] inclusive in-run sum of hits
   uint32_t* rid;                       // [n] run id

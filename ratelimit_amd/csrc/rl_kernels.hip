@@ -1579,8 +1579,10 @@ __device__ inline SegPair seg_chunk_scan(const SegChunk& c, uint32_t lane) {
 // is the concatenation, in tile (= arrival) order, of every tile's digit-d
 // segment; its size is the sum of the counts and its place in the sorted batch
 // the sum of the offsets (each offset counts the tile's smaller digits).
-// k_bucket: one 4-wave workgroup per bucket (several per CU, so one group's
-// barriers overlap another's work). It gathers the bucket, stably sorts it by
+// k_bucket: 4-wave workgroups, one per bucket or (a batch of mostly distinct
+// keys) BK_GRID of them walking the buckets; several per CU, so one group's
+// barriers overlap another's work. It gathers
+// the bucket (8-byte tile records, rl_tile.h), stably sorts it by
 // the remaining 22 key bits (three multisplit passes in LDS), so the batch ends
 // up sorted by the full key with arrival order kept within equal keys, and
 // segments it in place (runs never cross buckets): in-run inclusive sums of
@@ -1602,13 +1604,32 @@ struct BkShape {
 using BkSmall = BkShape<4, 8>;   // k_bucket: 2048 elements in LDS
 using BkBig = BkShape<8, 8>;     // k_bucket_big: 4096 elements per chunk (~62 KB of LDS: 2 workgroups per CU)
 
-#ifdef RL_BK_PROF  // bucketbench only: per-bucket phase stamps
+// Profiling builds only (RL_BK_PROF; scripts/stage_a_phases.py reads them
+// through rl_debug_stage_a_prof): per-bucket phase stamps of the bucket
+// kernels and per-tile ones of k_part, taken by thread 0 on the device's
+// constant-rate clock, after the wave's loads in flight. k_bucket: 0 start, 1 setup done, 2 gathered, 6 hashed
+// (duplicates flagged), 8 compacted and reserved, 3 sorted and written, 5
+// segmented. k_part: 0 start, 1 loaded, 2 ranked, 3 offsets scanned, 4
+// scattered in LDS, 5 written.
+#ifdef RL_BK_PROF
 __device__ unsigned long long g_bk_prof[PART_DIGITS * 16];
+__device__ unsigned long long g_part_prof[MAX_PART_TILES * 8];
 __device__ uint32_t g_bk_peel[PART_DIGITS * 16];  // peel state per bucket
-#define BK_STAMP(d, k) \
-  if (threadIdx.x == 0) g_bk_prof[(d) * 16 + (k)] = wall_clock64()
+// (a stamp waits for the wave's loads in flight, so a phase owns its own memory latency)
+#define PROF_WAIT() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory")
+#define BK_STAMP(d, k)                                        \
+  do {                                                        \
+    PROF_WAIT();                                              \
+    if (threadIdx.x == 0) g_bk_prof[(d) * 16 + (k)] = wall_clock64(); \
+  } while (0)
+#define PART_STAMP(t, k)                                      \
+  do {                                                        \
+    PROF_WAIT();                                              \
+    if (threadIdx.x == 0) g_part_prof[(t) * 8 + (k)] = wall_clock64(); \
+  } while (0)
 #else
 #define BK_STAMP(d, k)
+#define PART_STAMP(t, k)
 #endif
 
 // Wave-ballot multisplit on the BITS-bit digit at `shift`: rank of each item
@@ -1646,9 +1667,10 @@ __device__ inline void wave_multisplit(const uint32_t (&kk)[IT], uint32_t nvalid
   for (uint32_t i = 0; i < IT; i++) pos[i] = __shfl(pos[i] & 0xFFFFu, leader[i]) + (pos[i] >> 16);
 }
 
-// Exclusive scan of one value per thread over threads [0, 256) (waves 0..3);
-// every thread of the block must call it. *total = sum of the 256 values.
-__device__ inline uint32_t scan256(uint32_t v, uint32_t* wsum4, uint32_t* total) {
+// Exclusive scan of one value per thread over the threads of waves 0..W-1;
+// every thread of the block must call it. *total = sum of their values.
+template <uint32_t W>
+__device__ inline uint32_t scan_waves(uint32_t v, uint32_t* wsum, uint32_t* total) {
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint32_t inc = v;
 #pragma unroll
@@ -1656,39 +1678,57 @@ __device__ inline uint32_t scan256(uint32_t v, uint32_t* wsum4, uint32_t* total)
     const uint32_t y = __shfl_up(inc, off, 64);
     if (lane >= off) inc += y;
   }
-  if (wave < 4 && lane == 63) wsum4[wave] = inc;
+  if (wave < W && lane == 63) wsum[wave] = inc;
   __syncthreads();
-  uint32_t pre = 0;
+  uint32_t pre = 0, all = 0;
 #pragma unroll
-  for (uint32_t w = 0; w < 4; w++) pre += w < wave ? wsum4[w] : 0u;
-  if (total) *total = wsum4[0] + wsum4[1] + wsum4[2] + wsum4[3];
+  for (uint32_t w = 0; w < W; w++) {
+    pre += w < wave ? wsum[w] : 0u;
+    all += wsum[w];
+  }
+  if (total) *total = all;
   __syncthreads();
   return pre + inc - v;
 }
+// ... over threads [0, 256)
+__device__ inline uint32_t scan256(uint32_t v, uint32_t* wsum4, uint32_t* total) {
+  return scan_waves<4>(v, wsum4, total);
+}
 
-__global__ __launch_bounds__(256) void k_part(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ hin,
-                                              uint4* __restrict__ out, uint32_t n, uint32_t ntiles,
-                                              uint32_t* __restrict__ info, const uint32_t* err) {
-  constexpr uint32_t DPT = PART_DIGITS / 256;  // digits per thread
-  __shared__ uint32_t wcnt[4][PART_DIGITS];
-  __shared__ uint32_t wsum[4];
-  // the tile in partitioned order (key, index, hits), written out as whole lines
-  __shared__ uint32_t sk[PART_TILE], sv[PART_TILE], sh[PART_TILE];
+// k_part's LDS, used twice: the per-wave count rows of the multisplit, then
+// (every lane holding its items' tile positions in registers) the tile in
+// partitioned order, key and packed second word, written out as whole lines.
+constexpr uint32_t PART_LDS_WORDS =
+    PART_WAVES * PART_DIGITS > 2 * PART_TILE ? PART_WAVES * PART_DIGITS : 2 * PART_TILE;
+static_assert(PART_DIGITS % PART_THREADS == 0, "k_part: whole digits per thread");
+static_assert(PART_TILE < (1u << 16), "part_info packs a tile offset and a count into 16 bits each");
+
+__global__ __launch_bounds__(PART_THREADS) void k_part(const uint32_t* __restrict__ kin,
+                                                       const uint32_t* __restrict__ hin, TileRec* __restrict__ out,
+                                                       uint32_t n, uint32_t ntiles, uint32_t* __restrict__ info,
+                                                       const uint32_t* err) {
+  constexpr uint32_t DPT = PART_DIGITS / PART_THREADS;  // digits per thread
+  __shared__ uint32_t lds[PART_LDS_WORDS];
+  __shared__ uint32_t wsum[PART_WAVES];
+  uint32_t(*wcnt)[PART_DIGITS] = reinterpret_cast<uint32_t(*)[PART_DIGITS]>(lds);
+  uint32_t *sk = lds, *sp = lds + PART_TILE;
   if (*err) return;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tile = blockIdx.x;
-  for (uint32_t j = tid; j < 4 * PART_DIGITS; j += 256) (&wcnt[0][0])[j] = 0;
+  PART_STAMP(tile, 0);
+  for (uint32_t j = tid; j < PART_WAVES * PART_DIGITS; j += PART_THREADS) lds[j] = 0;
   __syncthreads();
-  const uint32_t wbase = tile * PART_TILE + wave * 64 * PART_ITEMS;
-  uint32_t kk[PART_ITEMS], vv[PART_ITEMS], hh[PART_ITEMS], pos[PART_ITEMS];
+  const uint32_t wbase = tile * PART_TILE + wave * 64 * PART_WITEMS;
+  uint32_t kk[PART_WITEMS], pv[PART_WITEMS], pos[PART_WITEMS];
 #pragma unroll
-  for (uint32_t i = 0; i < PART_ITEMS; i++) {
+  for (uint32_t i = 0; i < PART_WITEMS; i++) {
     const uint32_t j = min(wbase + i * 64 + lane, n - 1);  // unconditional loads, all in flight
     kk[i] = kin[j];
-    vv[i] = j;  // the descriptor index
-    hh[i] = hin[j];
+    pv[i] = tile_pack(0u, j, hin[j]).iv;  // the descriptor index and its hits (or the escape)
   }
-  wave_multisplit<PART_ITEMS, PART_BITS>(kk, wbase, n, 32 - PART_BITS, wcnt[wave], pos);
+  PART_STAMP(tile, 1);
+  wave_multisplit<PART_WITEMS, PART_BITS>(kk, wbase, n, 32 - PART_BITS, wcnt[wave], pos);
   __syncthreads();
+  PART_STAMP(tile, 2);
   // digits tid*DPT .. tid*DPT+DPT-1: per-wave exclusive offsets and counts,
   // then the tile's exclusive digit offsets (scan over threads)
   uint32_t c[DPT], tsum = 0;
@@ -1697,7 +1737,7 @@ __global__ __launch_bounds__(256) void k_part(const uint32_t* __restrict__ kin, 
     const uint32_t d = tid * DPT + j;
     uint32_t acc = 0;
 #pragma unroll
-    for (uint32_t w = 0; w < 4; w++) {
+    for (uint32_t w = 0; w < PART_WAVES; w++) {
       const uint32_t t = wcnt[w][d];
       wcnt[w][d] = acc;
       acc += t;
@@ -1705,37 +1745,40 @@ __global__ __launch_bounds__(256) void k_part(const uint32_t* __restrict__ kin, 
     c[j] = acc;
     tsum += acc;
   }
-  uint32_t excl = scan256(tsum, wsum, nullptr);
+  uint32_t excl = scan_waves<PART_WAVES>(tsum, wsum, nullptr);
 #pragma unroll
   for (uint32_t j = 0; j < DPT; j++) {
     const uint32_t d = tid * DPT + j;
     info[(size_t)d * ntiles + tile] = (excl << 16) | c[j];
 #pragma unroll
-    for (uint32_t w = 0; w < 4; w++) wcnt[w][d] += excl;  // rows now hold tile-relative bases
+    for (uint32_t w = 0; w < PART_WAVES; w++) wcnt[w][d] += excl;  // rows now hold tile-relative bases
     excl += c[j];
   }
   __syncthreads();
-  // Scatter into LDS, then stream the tile out with consecutive 16-B stores:
+#pragma unroll
+  for (uint32_t i = 0; i < PART_WITEMS; i++) pos[i] += wcnt[wave][kk[i] >> (32 - PART_BITS)];  // position in the tile
+  __syncthreads();  // the rows are read: their LDS becomes the staged tile
+  PART_STAMP(tile, 3);
+  // Scatter into LDS, then stream the tile out with consecutive 8-B stores:
   // scattering straight to HBM left ~4 records per digit segment, i.e. partial
   // 64-B lines (3.8x write amplification, profiles/r02/traffic_c1.json).
 #pragma unroll
-  for (uint32_t i = 0; i < PART_ITEMS; i++) {
+  for (uint32_t i = 0; i < PART_WITEMS; i++) {
     if (wbase + i * 64 + lane < n) {
-      const uint32_t d = kk[i] >> (32 - PART_BITS);
-      const uint32_t q = wcnt[wave][d] + pos[i];
-      sk[q] = kk[i];
-      sv[q] = vv[i];
-      sh[q] = hh[i];
+      sk[pos[i]] = kk[i];
+      sp[pos[i]] = pv[i];
     }
   }
   __syncthreads();
+  PART_STAMP(tile, 4);
   const uint32_t cnt = min(PART_TILE, n - tile * PART_TILE);
-  uint4* o = out + (size_t)tile * PART_TILE;
+  TileRec* o = out + (size_t)tile * PART_TILE;
 #pragma unroll
-  for (uint32_t i = 0; i < PART_ITEMS; i++) {
-    const uint32_t q = i * 256 + tid;
-    if (q < cnt) o[q] = make_uint4(sk[q], sv[q], sh[q], 0u);  // one 16-B record
+  for (uint32_t i = 0; i < PART_WITEMS; i++) {
+    const uint32_t q = i * PART_THREADS + tid;
+    if (q < cnt) o[q] = TileRec{sk[q], sp[q]};  // one 8-B record
   }
+  PART_STAMP(tile, 5);
 }
 
 // LDS of one bucket workgroup (the tile segment table is in dynamic LDS).
@@ -1788,6 +1831,19 @@ __device__ inline void bucket_src(uint32_t ntiles, const uint32_t (&p)[IT], uint
   }
 #pragma unroll
   for (uint32_t i = 0; i < IT; i++) j[i] = src[lo[i]] + p[i];
+}
+
+// Gather IT tile records and unpack them (tile_unpack): the 8-B loads first,
+// all in flight; a record with escaped hits then reads hin at its index.
+template <uint32_t IT>
+__device__ inline void tile_gather(const TileRec* __restrict__ pt, const uint32_t* __restrict__ hin,
+                                   const uint32_t (&jj)[IT], uint32_t (&kk)[IT], uint32_t (&vv)[IT],
+                                   uint32_t (&hh)[IT]) {
+  TileRec e[IT];
+#pragma unroll
+  for (uint32_t i = 0; i < IT; i++) e[i] = pt[jj[i]];
+#pragma unroll
+  for (uint32_t i = 0; i < IT; i++) tile_unpack(e[i], hin, kk[i], vv[i], hh[i]);
 }
 
 // Wave-sum of v over the block (all threads call); result in every thread.
@@ -2082,7 +2138,7 @@ constexpr uint32_t BIG_CNT = 1 + 2 * BK_HEAVY;  // per work item: light count, c
 // capacity and the whole bucket took the one-workgroup radix path, ~0.8 ms.)
 constexpr uint32_t BK_SAMPLES_PER_LANE = 4;
 template <typename B>
-__device__ inline void sample_heavy(BucketLds<B>& L, uint32_t S, uint32_t ntiles, const uint4* __restrict__ pt) {
+__device__ inline void sample_heavy(BucketLds<B>& L, uint32_t S, uint32_t ntiles, const TileRec* __restrict__ pt) {
   constexpr uint32_t R = BK_SAMPLES_PER_LANE, NS = 64 * R;
   const uint32_t lane = threadIdx.x & 63;
   if ((threadIdx.x >> 6) == 0) {
@@ -2093,7 +2149,7 @@ __device__ inline void sample_heavy(BucketLds<B>& L, uint32_t S, uint32_t ntiles
     bucket_src(ntiles, p, j);
 #pragma unroll
     for (uint32_t i = 0; i < R; i++) {
-      ks[i] = pt[j[i]].x;
+      ks[i] = pt[j[i]].key;
       cnt[i] = 0;
       first[i] = true;
     }
@@ -2129,25 +2185,33 @@ __device__ inline void sample_heavy(BucketLds<B>& L, uint32_t S, uint32_t ntiles
   __syncthreads();
 }
 
+// k_bucket's workgroups for a batch of mostly distinct keys, each walking the
+// buckets blockIdx.x, + BK_GRID, ... One workgroup per bucket keeps all 1024
+// resident at once (4 per CU: 16 waves and 140 KB of LDS) for the whole
+// kernel; for such a batch the pipeline's step is the table chain, not stage
+// A, so half the workgroups for longer is the better trade (C1 +2.8 %; 384 and
+// 256 no better, profiles/stage_a/). A sparse batch keeps a workgroup per bucket.
+constexpr uint32_t BK_GRID = 512;
+static_assert(BK_GRID < PART_DIGITS, "k_bucket<LIST, true> walks several buckets");
 #ifndef RL_BK_EARLY
 #define RL_BK_EARLY 1  // (A/B builds: 0 = bucket_segment counts and reserves the runs after the sort)
 #endif
 // LIST: the keys seen once are listed for k_table's singleton part (a batch
 // the host expects to be sparse: launch_stage_a); without it they are only
 // left out of the sorted order, and k_table answers them in arrival order.
+// One bucket d (every return is uniform over the workgroup).
 template <bool LIST>
-__global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
-    const uint4* __restrict__ pt,
+__device__ __attribute__((always_inline)) inline void bucket_one(
+    BucketLds<BkSmall>& L, const uint32_t d,
+    const TileRec* __restrict__ pt, const uint32_t* __restrict__ hin,
     const uint32_t* __restrict__ info, uint32_t ntiles, uint32_t* __restrict__ sk, uint32_t* __restrict__ sv,
     uint32_t* __restrict__ sh, uint32_t* __restrict__ segsum, uint32_t* __restrict__ rid,
     uint32_t* __restrict__ run_start, uint32_t* __restrict__ run_end, unsigned long long* num_runs,
     uint32_t* __restrict__ drun, BigMeta* __restrict__ meta, uint32_t* big_n, uint32_t* __restrict__ work,
-    uint32_t* work_n, uint32_t* sorted_n, uint2* __restrict__ uniq, uint32_t* uniq_n, const uint32_t* err,
+    uint32_t* work_n, uint32_t* sorted_n, uint2* __restrict__ uniq, uint32_t* uniq_n,
     uint32_t* big_hint) {
   using B = BkSmall;
-  __shared__ BucketLds<B> L;
-  if (*err) return;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, d = blockIdx.x;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   BK_STAMP(d, 0);
   bucket_setup(L, info, ntiles, d);
   const uint32_t S = L.S;
@@ -2185,13 +2249,7 @@ __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
 #pragma unroll
   for (uint32_t i = 0; i < B::ITEMS; i++) pp[i] = min(strip0 + i * 64 + lane, S - 1);
   bucket_src(ntiles, pp, jj);
-#pragma unroll
-  for (uint32_t i = 0; i < B::ITEMS; i++) {
-    const uint4 e = pt[jj[i]];
-    kk[i] = e.x;
-    vv[i] = e.y;
-    hh[i] = e.z;
-  }
+  tile_gather(pt, hin, jj, kk, vv, hh);
   BK_STAMP(d, 2);
   // Keys seen once in the batch never enter the sorted order: every
   // descriptor of a key falls in its bucket, so an LDS hash of the bucket's
@@ -2235,6 +2293,7 @@ __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
     }
   }
   __syncthreads();
+  BK_STAMP(d, 6);
   // compact the duplicated elements, keeping the bucket (= arrival) order,
   // count their keys (a key's first element that got the flag: the runs of
   // the sorted order, each of two or more) and, with LIST, rank the keys seen
@@ -2301,6 +2360,7 @@ __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
     for (uint32_t i = 0; i < B::ITEMS; i++)
       if ((smask >> i) & 1u) uniq[ub + sidx[i]] = make_uint2(vv[i], kk[i]);
   }
+  BK_STAMP(d, 8);
   if (!M) return;  // (uniform) every key of the bucket is seen once
   if (M <= 64) {
     // one wave: stable rank of (key, compact index) by comparisons
@@ -2354,6 +2414,31 @@ __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
   BK_STAMP(d, 5);
 }
 
+// WALK: the workgroup walks the buckets blockIdx.x, + gridDim.x, ... (a grid of
+// BK_GRID); else one bucket per workgroup (a grid of PART_DIGITS).
+template <bool LIST, bool WALK>
+__global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
+    const TileRec* __restrict__ pt, const uint32_t* __restrict__ hin,
+    const uint32_t* __restrict__ info, uint32_t ntiles, uint32_t* __restrict__ sk, uint32_t* __restrict__ sv,
+    uint32_t* __restrict__ sh, uint32_t* __restrict__ segsum, uint32_t* __restrict__ rid,
+    uint32_t* __restrict__ run_start, uint32_t* __restrict__ run_end, unsigned long long* num_runs,
+    uint32_t* __restrict__ drun, BigMeta* __restrict__ meta, uint32_t* big_n, uint32_t* __restrict__ work,
+    uint32_t* work_n, uint32_t* sorted_n, uint2* __restrict__ uniq, uint32_t* uniq_n, const uint32_t* err,
+    uint32_t* big_hint) {
+  __shared__ BucketLds<BkSmall> L;
+  if (*err) return;
+  if constexpr (WALK) {
+    for (uint32_t d = blockIdx.x; d < PART_DIGITS; d += gridDim.x) {
+      bucket_one<LIST>(L, d, pt, hin, info, ntiles, sk, sv, sh, segsum, rid, run_start, run_end, num_runs, drun, meta,
+                       big_n, work, work_n, sorted_n, uniq, uniq_n, big_hint);
+      __syncthreads();  // L and the segment table are reused by the next bucket
+    }
+  } else {
+    bucket_one<LIST>(L, blockIdx.x, pt, hin, info, ntiles, sk, sv, sh, segsum, rid, run_start, run_end, num_runs, drun,
+                     meta, big_n, work, work_n, sorted_n, uniq, uniq_n, big_hint);
+  }
+}
+
 // Large bucket dominated by a few keys (hot tenants): sample 64 positions;
 // keys seen at least BK_HEAVY_MIN times are "heavy". Pass A compacts the light
 // elements (arrival order) into LDS and counts each heavy key; the light ones
@@ -2363,7 +2448,7 @@ __global__ __launch_bounds__(BkSmall::THREADS, 4) void k_bucket(
 // do not fit in LDS.
 template <typename B>
 __device__ inline bool bucket_peel(BucketLds<B>& L, uint32_t d, uint32_t S, uint32_t base, uint32_t ntiles,
-                                   const uint4* __restrict__ pt,
+                                   const TileRec* __restrict__ pt, const uint32_t* __restrict__ hin,
                                    uint32_t* __restrict__ sk,
                                    uint32_t* __restrict__ sv, uint32_t* __restrict__ sh) {
   constexpr uint32_t IT = B::ITEMS;
@@ -2372,7 +2457,7 @@ __device__ inline bool bucket_peel(BucketLds<B>& L, uint32_t d, uint32_t S, uint
   if (wave == 0) {
     uint32_t p[1] = {(uint32_t)(((uint64_t)(2 * lane + 1) * S) >> 7)}, j[1];
     bucket_src(ntiles, p, j);
-    const uint32_t ks = pt[j[0]].x;
+    const uint32_t ks = pt[j[0]].key;
     uint32_t cnt = 0;
     bool first = true;
     for (uint32_t q = 0; q < 64; q++) {
@@ -2407,13 +2492,7 @@ __device__ inline bool bucket_peel(BucketLds<B>& L, uint32_t d, uint32_t S, uint
 #pragma unroll
     for (uint32_t i = 0; i < IT; i++) pp[i] = min(strip0 + i * 64 + lane, S - 1);
     bucket_src(ntiles, pp, jj);
-#pragma unroll
-    for (uint32_t i = 0; i < IT; i++) {
-      const uint4 e = pt[jj[i]];
-      kk[i] = e.x;
-      vv[i] = e.y;
-      hh[i] = e.z;
-    }
+    tile_gather(pt, hin, jj, kk, vv, hh);
     uint32_t wl = 0, lr[IT];
     uint32_t wc[BK_HEAVY];
 #pragma unroll
@@ -2522,13 +2601,7 @@ __device__ inline bool bucket_peel(BucketLds<B>& L, uint32_t d, uint32_t S, uint
 #pragma unroll
     for (uint32_t i = 0; i < IT; i++) pp[i] = min(s0 + i * 64 + lane, S - 1);
     bucket_src(ntiles, pp, jj);
-#pragma unroll
-    for (uint32_t i = 0; i < IT; i++) {
-      const uint4 e = pt[jj[i]];
-      kk[i] = e.x;
-      vv[i] = e.y;
-      hh[i] = e.z;
-    }
+    tile_gather(pt, hin, jj, kk, vv, hh);
     uint32_t hr[IT], wc[BK_HEAVY];
 #pragma unroll
     for (uint32_t c = 0; c < BK_HEAVY; c++) wc[c] = 0;
@@ -2584,7 +2657,7 @@ __device__ inline bool bucket_peel(BucketLds<B>& L, uint32_t d, uint32_t S, uint
 // afterwards). Running digit offsets per pass come from one histogram sweep.
 template <typename B>
 __device__ inline void bucket_lsd(BucketLds<B>& L, uint32_t S, uint32_t base, uint32_t ntiles,
-                                  const uint4* __restrict__ pt,
+                                  const TileRec* __restrict__ pt, const uint32_t* __restrict__ hin,
                                   uint32_t* __restrict__ sk,
                                   uint32_t* __restrict__ sv, uint32_t* __restrict__ sh, uint32_t* __restrict__ ht,
                                   uint32_t* __restrict__ segsum, uint32_t* __restrict__ rid) {
@@ -2599,7 +2672,7 @@ __device__ inline void bucket_lsd(BucketLds<B>& L, uint32_t S, uint32_t base, ui
     for (uint32_t i = 0; i < IT; i++) pp[i] = min(c0 + i * B::THREADS + tid, S - 1);
     bucket_src(ntiles, pp, jj);
 #pragma unroll
-    for (uint32_t i = 0; i < IT; i++) kk[i] = pt[jj[i]].x;  // loads first, all in flight
+    for (uint32_t i = 0; i < IT; i++) kk[i] = pt[jj[i]].key;  // loads first, all in flight
 #pragma unroll
     for (uint32_t i = 0; i < IT; i++) {
       if (c0 + i * B::THREADS + tid < S) {
@@ -2635,13 +2708,7 @@ __device__ inline void bucket_lsd(BucketLds<B>& L, uint32_t S, uint32_t base, ui
         for (uint32_t i = 0; i < IT; i++) jj[i] = pp[i];
       }
       if (pass == 0) {
-#pragma unroll
-        for (uint32_t i = 0; i < IT; i++) {
-          const uint4 e = pt[jj[i]];
-          kk[i] = e.x;
-          vv[i] = e.y;
-          hh[i] = e.z;
-        }
+        tile_gather(pt, hin, jj, kk, vv, hh);
       } else {
 #pragma unroll
         for (uint32_t i = 0; i < IT; i++) {
@@ -2714,22 +2781,17 @@ __device__ __attribute__((always_inline)) inline uint32_t wave_incl_add(uint32_t
 
 // Load one chunk of a queued bucket (BkSmall shape) and classify it: cls =
 // hot key index c < r, r for a light element, 0xFF past the bucket.
-__device__ inline void big_chunk_load(const BigMeta& M, uint32_t j, uint32_t ntiles, const uint4* __restrict__ pt,
-                                      uint32_t (&kk)[BkSmall::ITEMS], uint32_t (&vv)[BkSmall::ITEMS],
-                                      uint32_t (&hh)[BkSmall::ITEMS], uint32_t (&cls)[BkSmall::ITEMS], bool values) {
+__device__ inline void big_chunk_load(const BigMeta& M, uint32_t j, uint32_t ntiles, const TileRec* __restrict__ pt,
+                                      const uint32_t* __restrict__ hin, uint32_t (&kk)[BkSmall::ITEMS],
+                                      uint32_t (&vv)[BkSmall::ITEMS], uint32_t (&hh)[BkSmall::ITEMS],
+                                      uint32_t (&cls)[BkSmall::ITEMS]) {
   using B = BkSmall;
   const uint32_t lane = threadIdx.x & 63, s0 = j * BIG_CHUNK + (threadIdx.x >> 6) * B::STRIP;
   uint32_t pp[B::ITEMS], jj[B::ITEMS];
 #pragma unroll
   for (uint32_t i = 0; i < B::ITEMS; i++) pp[i] = min(s0 + i * 64 + lane, M.S - 1);
   bucket_src(ntiles, pp, jj);
-#pragma unroll
-  for (uint32_t i = 0; i < B::ITEMS; i++) {
-    const uint4 e = pt[jj[i]];
-    kk[i] = e.x;
-    hh[i] = e.z;
-    vv[i] = values ? e.y : 0u;
-  }
+  tile_gather(pt, hin, jj, kk, vv, hh);
 #pragma unroll
   for (uint32_t i = 0; i < B::ITEMS; i++) {
     cls[i] = s0 + i * 64 + lane < M.S ? M.r : 0xFFu;
@@ -2739,7 +2801,8 @@ __device__ inline void big_chunk_load(const BigMeta& M, uint32_t j, uint32_t nti
   }
 }
 
-__global__ __launch_bounds__(BkSmall::THREADS) void k_big_count(const uint4* __restrict__ pt,
+__global__ __launch_bounds__(BkSmall::THREADS) void k_big_count(const TileRec* __restrict__ pt,
+                                                                const uint32_t* __restrict__ hin,
                                                                 const uint32_t* __restrict__ info, uint32_t ntiles,
                                                                 const BigMeta* __restrict__ meta,
                                                                 const uint32_t* __restrict__ work,
@@ -2754,7 +2817,7 @@ __global__ __launch_bounds__(BkSmall::THREADS) void k_big_count(const uint4* __r
     const BigMeta M = meta[w >> 16];
     bucket_setup(L, info, ntiles, M.d);
     uint32_t kk[B::ITEMS], vv[B::ITEMS], hh[B::ITEMS], cls[B::ITEMS];
-    big_chunk_load(M, w & 0xFFFFu, ntiles, pt, kk, vv, hh, cls, false);
+    big_chunk_load(M, w & 0xFFFFu, ntiles, pt, hin, kk, vv, hh, cls);
     uint32_t nl = 0, nc[BK_HEAVY], hs[BK_HEAVY];
 #pragma unroll
     for (uint32_t c = 0; c < BK_HEAVY; c++) nc[c] = hs[c] = 0;
@@ -2794,7 +2857,7 @@ __global__ __launch_bounds__(BkSmall::THREADS) void k_big_count(const uint4* __r
 }
 
 __global__ __launch_bounds__(BkSmall::THREADS) void k_big_place(
-    const uint4* __restrict__ pt,
+    const TileRec* __restrict__ pt, const uint32_t* __restrict__ hin,
     const uint32_t* __restrict__ info, uint32_t ntiles, const BigMeta* __restrict__ meta,
     const uint32_t* __restrict__ work, const uint32_t* work_n, const uint32_t* __restrict__ cnt,
     uint32_t* __restrict__ sk, uint32_t* __restrict__ sv, uint32_t* __restrict__ sh, uint32_t* __restrict__ segsum,
@@ -2841,7 +2904,7 @@ __global__ __launch_bounds__(BkSmall::THREADS) void k_big_place(
       drun[M.db_heavy + tid] = M.rb_heavy + tid;
     }
     uint32_t kk[B::ITEMS], vv[B::ITEMS], hh[B::ITEMS], cls[B::ITEMS];
-    big_chunk_load(M, j, ntiles, pt, kk, vv, hh, cls, true);
+    big_chunk_load(M, j, ntiles, pt, hin, kk, vv, hh, cls);
     // ranks in the chunk (item-major within the wave strip = arrival order):
     // light rank, and per hot key: rank and inclusive sum of max(1, hits)
     uint32_t rk[B::ITEMS], hp[B::ITEMS], wl = 0, wc[BK_HEAVY], wh[BK_HEAVY];
@@ -2920,7 +2983,7 @@ __global__ __launch_bounds__(BkSmall::THREADS) void k_big_place(
 }
 
 __global__ __launch_bounds__(BkBig::THREADS) void k_bucket_big(
-    const uint4* __restrict__ pt,
+    const TileRec* __restrict__ pt, const uint32_t* __restrict__ hin,
     const uint32_t* __restrict__ info, uint32_t ntiles, uint32_t* __restrict__ sk, uint32_t* __restrict__ sv,
     uint32_t* __restrict__ sh, uint32_t* __restrict__ ht, uint32_t* __restrict__ segsum, uint32_t* __restrict__ rid,
     uint32_t* __restrict__ run_start, uint32_t* __restrict__ run_end, unsigned long long* num_runs,
@@ -2969,8 +3032,8 @@ __global__ __launch_bounds__(BkBig::THREADS) void k_bucket_big(
       if (tid < M.r) run_start[M.rb_heavy + tid] = run_end[M.rb_heavy + tid] = 0;  // hot-key runs left empty
       bucket_setup(L, info, ntiles, d);
       BK_STAMP(d, 1);
-      if (!bucket_peel(L, d, S, base, ntiles, pt, sk, sv, sh))
-        bucket_lsd(L, S, base, ntiles, pt, sk, sv, sh, ht, segsum, rid);
+      if (!bucket_peel(L, d, S, base, ntiles, pt, hin, sk, sv, sh))
+        bucket_lsd(L, S, base, ntiles, pt, hin, sk, sv, sh, ht, segsum, rid);
       bucket_segment<B, false>(L, d, S, base, sk, sh, segsum, rid, run_start, run_end, num_runs, drun);
     }
     BK_STAMP(d, 7);
@@ -5830,6 +5893,15 @@ __global__ __launch_bounds__(256) void k_debug_decide(uint32_t n, const uint32_t
 // ===========================================================================
 // Launch wrappers
 // ===========================================================================
+#ifdef RL_BK_PROF
+// The stamps of the last stage A that ran: bk[PART_DIGITS x 16], part[MAX_PART_TILES x 8].
+extern "C" __attribute__((visibility("default"))) int rl_debug_stage_a_prof(unsigned long long* bk,
+                                                                            unsigned long long* part) {
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  if (hipMemcpyFromSymbol(bk, HIP_SYMBOL(g_bk_prof), sizeof(g_bk_prof)) != hipSuccess) return 1;
+  return hipMemcpyFromSymbol(part, HIP_SYMBOL(g_part_prof), sizeof(g_part_prof)) != hipSuccess;
+}
+#endif
 static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
 // Stage A (table-free): validate, hash, sort, segment, and mark the descriptors
@@ -5846,23 +5918,27 @@ void launch_stage_a(const BatchDev& b, const Scratch& s, int isolate, int per_se
                                   s.work_n, s.run_flags, s.runs64, s.hit_a, s.res, s.sorted_n, s.uniq_n);
   if (ev) (void)hipEventRecord(ev[1], st);
   const uint32_t ptiles = cdiv(b.n, PART_TILE);
+  const uint32_t* hin = b.wire ? s.hit_a : b.hits;  // k_part's hits, and the tile readers' for an escaped record
   if (b.n)
-    k_part<<<ptiles, 256, 0, st>>>(s.keys[0], b.wire ? s.hit_a : b.hits, s.tile, b.n, ptiles, s.part_info, s.err);
+    k_part<<<ptiles, PART_THREADS, 0, st>>>(s.keys[0], hin, s.tile, b.n, ptiles, s.part_info, s.err);
   if (ev) (void)hipEventRecord(ev[2], st);
   if (b.n) {
     const size_t seg_lds = (2ull * ptiles + 1) * 4;
-    (list_on ? k_bucket<true> : k_bucket<false>)<<<PART_DIGITS, BkSmall::THREADS, seg_lds, st>>>(
-        s.tile, s.part_info, ptiles, s.keys[1], s.vals[0], s.hits_s, s.segsum, s.rid, s.run_start, s.run_end,
+    // A sparse batch (list_on: the host's cue, many and long runs) has the longer stage A: its buckets get a
+    // workgroup each. A batch of mostly distinct keys waits for the table chain: half the workgroups.
+    (list_on ? k_bucket<true, false> : k_bucket<false, true>)
+        <<<list_on ? PART_DIGITS : BK_GRID, BkSmall::THREADS, seg_lds, st>>>(
+        s.tile, hin, s.part_info, ptiles, s.keys[1], s.vals[0], s.hits_s, s.segsum, s.rid, s.run_start, s.run_end,
         s.runs64, s.drun, s.big_meta, s.big_n, s.big_work, s.work_n, s.sorted_n, s.uniq, s.uniq_n, s.err, big_hint);
 #ifndef RL_EXP_NO_BIG  // (measurement builds only: without the large-bucket kernels, C1 has none)
     const uint32_t gi = big_full ? BIG_ITEM_BLOCKS : 1u, gb = big_full ? BIG_BLOCKS : 1u;
-    k_big_count<<<gi, BkSmall::THREADS, seg_lds, st>>>(s.tile, s.part_info, ptiles,
+    k_big_count<<<gi, BkSmall::THREADS, seg_lds, st>>>(s.tile, hin, s.part_info, ptiles,
                                                                     s.big_meta, s.big_work, s.work_n, s.big_cnt,
                                                                     s.err);
     k_big_place<<<gi, BkSmall::THREADS, seg_lds, st>>>(
-        s.tile, s.part_info, ptiles, s.big_meta, s.big_work, s.work_n, s.big_cnt, s.keys[1],
+        s.tile, hin, s.part_info, ptiles, s.big_meta, s.big_work, s.work_n, s.big_cnt, s.keys[1],
         s.vals[0], s.hits_s, s.segsum, s.rid, s.run_start, s.run_end, s.drun, s.err);
-    k_bucket_big<<<gb, BkBig::THREADS, seg_lds, st>>>(s.tile, s.part_info, ptiles,
+    k_bucket_big<<<gb, BkBig::THREADS, seg_lds, st>>>(s.tile, hin, s.part_info, ptiles,
                                                               s.keys[1], s.vals[0], s.hits_s, s.hit_t, s.segsum,
                                                               s.rid, s.run_start, s.run_end, s.runs64, s.drun, s.big_meta,
                                                               s.big_n, s.big_cnt, s.err);
