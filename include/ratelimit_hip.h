@@ -1249,6 +1249,84 @@ typedef struct rl_resize_info {
 } rl_resize_info;
 int rl_resize(rl_ctx* ctx, uint64_t table_slots, rl_resize_info* info /* may be NULL */);
 
+/* ---- Delete keys by stem or by stem prefix (Redis DEL, SCAN MATCH + DEL) ------
+ * rl_forget removes stems from the table on the device: the tenant that a
+ * misconfigured limit blocked, the old window's count after a limit was
+ * raised, a decommissioned domain. Without it a key leaves the table only
+ * when every one of its windows and its local-cache entry has expired and a
+ * sweep sees that.
+ *
+ * What is removed: a stem is removed whole, every unit slot it has, and with
+ * each slot its newest window, its chain of older windows and its local
+ * over-limit cache entries. Each removed slot gets tag = TAG_TOMB and ring =
+ * LOG_NONE, exactly what rl_sweep's eviction leaves behind; its log entries
+ * are left to be overwritten. In Redis terms: DEL of every key
+ * stem ‖ decimal(ws) in both stores, plus the freecache entries of those keys.
+ * There is deliberately no per-unit or per-window deletion: under the alias
+ * rule unit slots of one stem stand for the same Redis key where
+ * their windows coincide, and a partial delete would leave the key alive
+ * through a sibling. Afterwards a request or rl_lookup for the stem behaves
+ * as for a stem never seen: not found, count 0, no local-cache hit, a fresh
+ * slot on the next hit.
+ *
+ * Keyed mode (no RL_FORGET_PREFIX): entry i is a whole stem, removed[i] the
+ * number of its unit slots removed (0..4, 0 if absent). A stem given twice is
+ * counted once, under either entry. Whole-call failures write nothing: a null
+ * `in` (or array in it), bad offsets (stem_off[0] != 0, decreasing), unknown
+ * flags, an empty stem or one over 65535 bytes RL_E_INVALID; n > max_batch or
+ * stem bytes > max_stem_bytes RL_E_CAPACITY.
+ *
+ * Prefix mode (RL_FORGET_PREFIX): every entry is a stem prefix. A live slot
+ * matches entry i when its stem is at least as long as the prefix and begins
+ * with the prefix's bytes; the slot is counted under the lowest matching i.
+ * One scan of the table serves all prefixes of the call. Whole-call failures,
+ * beside the keyed mode's RL_E_INVALID ones: an empty prefix RL_E_INVALID
+ * (there is no "flush everything"); n > RL_FORGET_PREFIX_MAX or their bytes >
+ * RL_FORGET_PREFIX_BYTES RL_E_CAPACITY. Prefixes are bytes, not descriptor
+ * entries: the reference's key format (domain_key_value_...) makes "a_" a
+ * prefix of both domain "a" and domain "a_b", exactly as a Redis
+ * SCAN MATCH a_* would see it.
+ *
+ * RL_FORGET_DRY_RUN: the same removed[] and *info as the real call would give
+ * at that moment (with a stem listed more than once: the same sums); no byte
+ * of the ctx changes.
+ *
+ * Ordering: the call orders after every submitted batch (it completes pending
+ * second halves of the packed and wire paths, host-fed batches and the
+ * progress ring, as rl_export_range and rl_resize do), is synchronous and
+ * holds the batch pipeline for its duration.
+ *
+ * Untouched: the sweep floor, history_appended / _lost / _refused, batches,
+ * decisions, the loaded config, the override-rule table and the local-cache
+ * hit / miss counters. rl_table_info.live_slots drops by info->keys and
+ * tombstones rises by the same amount (exact_stems and history_slots by the
+ * removed slots that were flagged / had a chain); the slots become empty again
+ * at the next rl_sweep under its reclamation rule, and the arena's bytes come
+ * back at that sweep's compaction.
+ *
+ * A multi-shard ctx routes keyed stems to their owners on the host and
+ * scatters removed[] back, like rl_lookup; prefixes go to every shard
+ * concurrently, removed[] and *info summed. The whole call is checked before
+ * any shard changes anything. RL_E_INVALID on a ctx that joined a
+ * communicator. n == 0: RL_OK, *info zero. */
+#define RL_FORGET_PREFIX  0x1u   /* every entry is a stem prefix, not a whole stem */
+#define RL_FORGET_DRY_RUN 0x2u   /* select and count, change nothing */
+#define RL_FORGET_PREFIX_MAX   64u    /* prefixes per call */
+#define RL_FORGET_PREFIX_BYTES 4096u  /* their bytes per call */
+typedef struct rl_stems {        /* host memory */
+  uint32_t n, flags;             /* RL_FORGET_* */
+  const uint8_t* stem_bytes;
+  const uint32_t* stem_off;      /* n + 1, stem_off[0] == 0 */
+} rl_stems;
+typedef struct rl_forget_info {  /* 32 bytes */
+  uint64_t slots_scanned;        /* prefix mode: slots read, summed over shards; keyed mode: 0 */
+  uint64_t keys;                 /* (stem, unit) slots removed (dry run: that would be) */
+  uint64_t keys_with_history;    /* of them, slots whose history chain was not empty */
+  uint64_t arena_bytes;          /* long-stem arena bytes the next sweep's compaction gets back */
+} rl_forget_info;
+int rl_forget(rl_ctx* ctx, const rl_stems* in, uint32_t* removed /* [n] or NULL */,
+              rl_forget_info* info /* may be NULL */);
+
 /* Per-stage device timing (HIP events on the batch stream), for benchmarks.
  * rl_profile(ctx, k) with k >= 1 starts accumulating over every k-th batch,
  * the first sampled one being the k-th submitted after the call (1 = every

@@ -270,6 +270,23 @@ class RlResizeInfo(C.Structure):
                 ("longest_probe", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+RL_FORGET_PREFIX = 1   # rl_stems.flags: every entry is a stem prefix, not a whole stem
+RL_FORGET_DRY_RUN = 2  # select and count, change nothing
+RL_FORGET_PREFIX_MAX = 64      # prefixes per call
+RL_FORGET_PREFIX_BYTES = 4096  # their bytes per call
+
+
+class RlStems(C.Structure):
+    """rl_stems: the stems (or stem prefixes) of one rl_forget call."""
+    _fields_ = [("n", C.c_uint32), ("flags", C.c_uint32), ("stem_bytes", P), ("stem_off", P)]
+
+
+class RlForgetInfo(C.Structure):
+    """rl_forget_info: what one rl_forget removed (summed over shards)."""
+    _fields_ = [("slots_scanned", C.c_uint64), ("keys", C.c_uint64), ("keys_with_history", C.c_uint64),
+                ("arena_bytes", C.c_uint64)]
+
+
 RL_MATCH_NONE, RL_MATCH_UNLIMITED, RL_MATCH_LIMIT = 0, 1, 2
 REQUEST_ARRAYS = ("domain_bytes", "domain_off", "now", "hits", "req_idx", "entry_first", "desc_off", "desc_bytes",
                   "key_len", "value_len", "override_flags", "override_rpu", "override_unit", "override_rule")

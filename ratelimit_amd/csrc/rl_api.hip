@@ -49,7 +49,7 @@ constexpr uint32_t MAX_LOCAL_SHARDS = 16;
 
 // One shard's worker: runs its router's collective steps on its own thread.
 struct ShardWorker {
-  enum Job { IDLE, BATCH, SYNC, RESIZE, EXIT };
+  enum Job { IDLE, BATCH, SYNC, RESIZE, FORGET, EXIT };
   std::thread th;
   std::mutex mu;
   std::condition_variable cv;
@@ -60,6 +60,9 @@ struct ShardWorker {
   hipStream_t caller = nullptr;
   uint64_t rs_slots = 0;  // RESIZE: the new slot count, and what the shard placed
   ResizePlan rs_plan;
+  const rl_stems* fg_in = nullptr;  // FORGET: the call's prefixes, and this shard's answer
+  uint32_t fg_removed[RL_FORGET_PREFIX_MAX] = {};
+  rl_forget_info fg_info{};
   int rc = RL_OK;
 };
 
@@ -133,6 +136,8 @@ void worker_main(rl_ctx* c, uint32_t j) {
       rc = comm_do_limit(c->r[j], c->e[j], &w.in, &w.out, w.caller, &w.io);
     } else if (job == ShardWorker::RESIZE) {  // (the placement only: rl_resize commits once every shard has placed)
       rc = eng_resize_place(c->e[j], w.rs_slots, &w.rs_plan);
+    } else if (job == ShardWorker::FORGET) {  // (prefix mode: every shard scans its own table)
+      rc = eng_forget(c->e[j], w.fg_in, w.fg_removed, &w.fg_info);
     } else {  // SYNC: the pending batch (collective), the router's streams, then the engine's error words
       rc = comm_synchronize(c->r[j], c->e[j]);
       const int re = eng_synchronize(c->e[j]);
@@ -913,6 +918,73 @@ int rl_lookup(rl_ctx* c, const rl_keys* in, rl_key_state* out) {
       out->expire[i] = sub[j].expire[x];
       out->lc[i] = sub[j].lc[x];
     }
+  return RL_OK;
+}
+
+int rl_forget(rl_ctx* c, const rl_stems* in, uint32_t* removed, rl_forget_info* info) {
+  // (a single-shard ctx reports through its engine: rl_last_error reads it there)
+  auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };
+  if (!c || !in) return bad(RL_E_INVALID, "gpu: null argument");
+  if (c->comm) return bad(RL_E_INVALID, "gpu: rl_forget is not for a ctx that joined a communicator");
+  if (c->n == 1) return eng_forget(c->e[0], in, removed, info);
+  // the whole call is checked first: a bad call changes no shard
+  if (const int rc = from_engine(c, c->e[0], eng_forget_check(c->e[0], in))) return rc;
+  if (const int src = settle_local(c)) return src;
+  const uint32_t N = c->n;
+  rl_forget_info sum{};
+  if (!in->n) {
+    if (info) *info = sum;
+    return RL_OK;
+  }
+  auto add = [&](const rl_forget_info& x) {
+    sum.slots_scanned += x.slots_scanned;
+    sum.keys += x.keys;
+    sum.keys_with_history += x.keys_with_history;
+    sum.arena_bytes += x.arena_bytes;
+  };
+  if (in->flags & RL_FORGET_PREFIX) {
+    // every shard scans its own table on its own device and worker, for all the prefixes
+    for (uint32_t j = 0; j < N; j++) c->w[j].fg_in = in;
+    if (const int rc = run_shards(c, ShardWorker::FORGET)) return rc;
+    for (uint32_t j = 0; j < N; j++) add(c->w[j].fg_info);
+    if (removed)
+      for (uint32_t i = 0; i < in->n; i++) {
+        removed[i] = 0;
+        for (uint32_t j = 0; j < N; j++) removed[i] += c->w[j].fg_removed[i];
+      }
+    if (info) *info = sum;
+    return RL_OK;
+  }
+  // keyed stems go to their owners, routed on the host like rl_lookup's keys,
+  // and the counts come back in the caller's order
+  std::vector<std::vector<uint32_t>> idx(N);
+  for (uint32_t i = 0; i < in->n; i++) {
+    const uint32_t a = in->stem_off[i], b = in->stem_off[i + 1];
+    idx[owner_of_host(hash_stem_host(c->e[0]->hk, in->stem_bytes + a, b - a), N)].push_back(i);
+  }
+  std::vector<std::vector<uint32_t>> got(N);
+  for (uint32_t j = 0; j < N; j++) {
+    if (idx[j].empty()) continue;
+    std::vector<uint8_t> stems;
+    std::vector<uint32_t> off{0};
+    for (uint32_t i : idx[j]) {
+      stems.insert(stems.end(), in->stem_bytes + in->stem_off[i], in->stem_bytes + in->stem_off[i + 1]);
+      off.push_back((uint32_t)stems.size());
+    }
+    got[j].resize(idx[j].size());
+    rl_stems sub{};
+    sub.n = (uint32_t)idx[j].size();
+    sub.flags = in->flags;
+    sub.stem_bytes = stems.data();
+    sub.stem_off = off.data();
+    rl_forget_info x{};
+    if (const int rc = from_engine(c, c->e[j], eng_forget(c->e[j], &sub, got[j].data(), &x))) return rc;
+    add(x);
+  }
+  if (removed)
+    for (uint32_t j = 0; j < N; j++)
+      for (size_t x = 0; x < idx[j].size(); x++) removed[idx[j][x]] = got[j][x];
+  if (info) *info = sum;
   return RL_OK;
 }
 

@@ -137,6 +137,7 @@ struct Engine {
   uint8_t* arena = nullptr;
   uint8_t* arena2 = nullptr;  // compaction target (rl_sweep), swapped with arena
   uint64_t arena_cap16 = 0;
+  bool arena_forgotten = false;  // rl_forget removed long stems: the next sweep compacts the arena even if it evicts nothing
   uint64_t hot_range = 1ull << 22;  // slots per scan range of eng_hot_keys (RL_HOT_RANGE: tests cross ranges on tiny tables)
   // scratch: s[k] per buffer; stripes, counters, time floor, routing and the
   // table-stage error word are shared
@@ -344,6 +345,12 @@ struct HotAnswer {
 };
 int eng_hot_check(Engine* c, const rl_hot_query* q);
 int eng_hot_keys(Engine* c, const rl_hot_query* q, HotAnswer* ans, rl_hot_info* info);
+// rl_forget's whole-call checks against this engine's limits (host only;
+// eng_forget runs them too), and the deletion on this engine's table: keyed
+// stems through the staging of the host-buffer entry points, prefixes by one
+// scan. removed ([in->n]) and info may be null; *info is this engine's alone.
+int eng_forget_check(Engine* c, const rl_stems* in);
+int eng_forget(Engine* c, const rl_stems* in, uint32_t* removed, rl_forget_info* info);
 // rl_resize on this engine. One call (eng_resize), or in two steps for a ctx of
 // several shards: eng_resize_place puts every live key into a new table beside
 // the old one and changes nothing of the engine (any failure leaves the plan

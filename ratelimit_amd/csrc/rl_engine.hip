@@ -1350,9 +1350,11 @@ int eng_sweep(Engine* c, int64_t now, uint64_t* n_evicted) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (n_evicted) *n_evicted = c->h_counters[0];
   const uint64_t n_used = c->h_counters[1];  // live slots and tombstones after the eviction
-  if (c->h_counters[0] && c->h_counters[4]) {
+  if ((c->h_counters[0] || c->arena_forgotten) && c->h_counters[4]) {
     // reclaim the long-stem arena: live slots' overflow bytes move to the spare
-    // arena, packed from 0, and the two swap (counters[4] = the arena cursor)
+    // arena, packed from 0, and the two swap (counters[4] = the arena cursor);
+    // also after an rl_forget that removed long stems, whatever this sweep evicted
+    c->arena_forgotten = false;
     HIPCHK(c, hipMemsetAsync(c->s[0].counters + 4, 0, 8, c->stream));
     launch_arena_compact(c->slots, c->nslots, c->arena, c->arena2, c->s[0].counters + 4, c->stream);
     HIPCHK(c, hipGetLastError());
@@ -3203,6 +3205,82 @@ int eng_lookup(Engine* c, const rl_keys* in, rl_key_state* out) {
   HIPCHK(c, hipMemcpyAsync(out->expire, q.expire, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipMemcpyAsync(out->lc, q.lc, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));  // (now32 lives until here)
+  return RL_OK;
+}
+
+int eng_forget_check(Engine* c, const rl_stems* in) {
+  if (!c || !in) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (in->flags & ~(RL_FORGET_PREFIX | RL_FORGET_DRY_RUN)) return set_err(c, RL_E_INVALID, "gpu: rl_forget: unknown flags");
+  const bool prefix = in->flags & RL_FORGET_PREFIX;
+  const uint32_t n = in->n;
+  if (prefix ? n > RL_FORGET_PREFIX_MAX : n > c->cfg.max_batch)
+    return set_err(c, RL_E_CAPACITY, prefix ? "gpu: rl_forget: more than RL_FORGET_PREFIX_MAX prefixes"
+                                            : "gpu: rl_forget exceeds configured max_batch");
+  if (!n) return RL_OK;
+  if (!in->stem_bytes || !in->stem_off) return set_err(c, RL_E_INVALID, "gpu: null rl_stems array");
+  if (in->stem_off[0] != 0) return set_err(c, RL_E_INVALID, "gpu: rl_forget stem offsets must start at 0");
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t a = in->stem_off[i], b = in->stem_off[i + 1];
+    if (b <= a || b - a > 65535u)  // (no empty prefix either: there is no "flush everything")
+      return set_err(c, RL_E_INVALID, "gpu: rl_forget entry " + std::to_string(i) + ": stem offsets (1..65535 bytes)");
+  }
+  if (in->stem_off[n] > (prefix ? RL_FORGET_PREFIX_BYTES : c->cfg.max_stem_bytes))
+    return set_err(c, RL_E_CAPACITY, prefix ? "gpu: rl_forget: more than RL_FORGET_PREFIX_BYTES bytes of prefixes"
+                                            : "gpu: rl_forget exceeds configured max_stem_bytes");
+  return RL_OK;
+}
+
+int eng_forget(Engine* c, const rl_stems* in, uint32_t* removed, rl_forget_info* info) {
+  if (const int rc = eng_forget_check(c, in)) return rc;
+  RQ_SETTLE(c);
+  if (info) *info = rl_forget_info{};
+  const uint32_t n = in->n;
+  if (!n) return RL_OK;
+  const uint32_t nb = in->stem_off[n];
+  const bool prefix = in->flags & RL_FORGET_PREFIX;
+  const uint32_t dry = in->flags & RL_FORGET_DRY_RUN ? 1u : 0u;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream;
+  HIPCHK(c, after_batches(c, st));  // (the staging below is the synchronous entry points': free by then)
+  unsigned long long* ctr = c->s[0].counters;  // (words 0..2: scratch of the synchronous calls, as rl_sweep's)
+  HIPCHK(c, hipMemsetAsync(ctr, 0, 24, st));
+  DevBufs mem;
+  uint32_t* d_removed = c->d_rem;
+  if (prefix) {
+    uint8_t* d_pfx = nullptr;
+    uint32_t* d_poff = nullptr;
+    HIPCHK(c, mem.get(&d_pfx, (size_t)RL_FORGET_PREFIX_BYTES));
+    HIPCHK(c, mem.get(&d_poff, (size_t)RL_FORGET_PREFIX_MAX + 1));
+    HIPCHK(c, mem.get(&d_removed, (size_t)RL_FORGET_PREFIX_MAX));
+    HIPCHK(c, hipMemsetAsync(d_pfx, 0, RL_FORGET_PREFIX_BYTES, st));
+    HIPCHK(c, hipMemsetAsync(d_removed, 0, RL_FORGET_PREFIX_MAX * 4, st));
+    HIPCHK(c, hipMemcpyAsync(d_pfx, in->stem_bytes, nb, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_poff, in->stem_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));
+    launch_forget_scan(table_view(c), c->nslots, d_pfx, d_poff, n, dry, ctr, d_removed, st);
+  } else {
+    uint32_t* claim = nullptr;
+    if (dry) {  // one bit per slot, for this call only: a dry run claims there what the real call claims in the tags
+      const size_t words = (size_t)((c->nslots + 31) / 32);
+      HIPCHK(c, mem.get(&claim, words));
+      HIPCHK(c, hipMemsetAsync(claim, 0, words * 4, st));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_stem, in->stem_bytes, nb, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->d_off, in->stem_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));
+    const ForgetDev q{n, c->d_off, d_removed, ctr, claim, dry};
+    launch_forget_keys(table_view(c), c->hk, c->d_stem, nb, q, st);
+  }
+  HIPCHK(c, hipGetLastError());
+  unsigned long long h[3] = {};
+  HIPCHK(c, hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
+  if (removed) HIPCHK(c, hipMemcpyAsync(removed, d_removed, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (!dry && h[2]) c->arena_forgotten = true;
+  if (info) {
+    info->slots_scanned = prefix ? c->nslots : 0;
+    info->keys = h[0];
+    info->keys_with_history = h[1];
+    info->arena_bytes = h[2] * 16;
+  }
   return RL_OK;
 }
 

@@ -466,6 +466,29 @@ struct LookupDev {
 // key and nothing else: no slot, no arena space, no log entry, no counter.
 void launch_lookup(const TableDev& t, const HashKey& hk, const Params& P, const int64_t* time_floor,
                    const uint8_t* stem, uint32_t stem_total, const LookupDev& q, hipStream_t st);
+// ---- deletion by stem or stem prefix (rl_forget) ----
+// Device staging of one keyed call. ctr: 3 zeroed words, += slots removed, of
+// them with a history chain, their arena space in 16-B units. dry != 0:
+// nothing of the table is written and `claim`, (nslots + 31) / 32 zeroed
+// words of the call's own, takes the claims (else unused).
+struct ForgetDev {
+  uint32_t n;
+  const uint32_t* off;  // n + 1 stem offsets
+  uint32_t* removed;    // [n] unit slots removed per entry
+  unsigned long long* ctr;
+  uint32_t* claim;
+  uint32_t dry;
+};
+// Stems as launch_lookup takes them (one lane per stem, k_forget_keys).
+void launch_forget_keys(const TableDev& t, const HashKey& hk, const uint8_t* stem, uint32_t stem_total,
+                        const ForgetDev& q, hipStream_t st);
+// The prefix mode's full-table scan (rl_forget.hip, k_forget_scan). pfx:
+// RL_FORGET_PREFIX_BYTES readable bytes, 16-B aligned, the np <=
+// RL_FORGET_PREFIX_MAX prefixes packed at poff[0..np] (none empty). removed:
+// [np] zeroed words, += the slots counted under each prefix (the lowest that
+// matches); ctr as ForgetDev's. dry != 0: nothing is written but those.
+void launch_forget_scan(const TableDev& t, uint64_t nslots, const uint8_t* pfx, const uint32_t* poff, uint32_t np,
+                        uint32_t dry, unsigned long long* ctr, uint32_t* removed, hipStream_t st);
 // ---- the busiest / blocked keys (rl_hot_keys, rl_hot.hip): a read-only scan ----
 // One call's device state (zero at its start).
 struct HotState {

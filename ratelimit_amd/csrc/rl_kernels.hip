@@ -5846,6 +5846,73 @@ __global__ __launch_bounds__(256) void k_lookup(const TableDev t, const BatchDev
 }
 
 // ===========================================================================
+// Keyed deletion (rl_forget without RL_FORGET_PREFIX): Redis DEL of every key
+// of a stem. One lane per stem, staged and hashed as k_lookup does; the lane
+// walks the stem's probe sequence from its home to the first empty slot (or
+// max_probe) like find_unit_slots, but takes every slot whose tag is the
+// stem's under the slot's own unit and whose full stem matches (inline bytes
+// and arena): each becomes what k_sweep leaves behind, tag = TAG_TOMB and
+// ring = LOG_NONE, its log entries left to be overwritten.
+// Two lanes may hold the same stem, so a slot is claimed: atomicCAS(tag, seen,
+// TAG_TOMB), and only the winner counts it and stores ring. A dry run changes
+// no byte of the table, so it claims the slot's bit in a bitmap of one bit per
+// slot that belongs to the call (atomicOr: the lane that finds the bit clear
+// counts the slot). Either way a stem listed more than once is counted once,
+// under whichever of its entries won, and the two modes' sums are equal.
+// ctr[0] += slots removed, [1] += of them with a history chain, [2] += their
+// arena space in 16-B units: folded per workgroup, one atomic each.
+// ===========================================================================
+__global__ __launch_bounds__(256) void k_forget_keys(const TableDev t, const BatchDev b, const ForgetDev q) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  unsigned long long v[3] = {0, 0, 0};
+  if (i < q.n) {
+    const uint32_t s0 = q.off[i], s1 = q.off[i + 1];
+    uint32_t cnt = 0;
+    if (s1 > s0 && s1 - s0 <= 65535u && s1 <= b.stem_total) {  // (the host has checked the offsets)
+      Rec r0{};
+      r0.off = s0;
+      r0.lu = s1 - s0;
+      const Key key = key_of(b, r0);
+      uint64_t hs = hash_key(b.hk, key);
+      if ((uint32_t)(hs >> 32) == KEY_DUP) hs = ((uint64_t)(KEY_DUP - 1u) << 32) | (uint32_t)hs;  // (as k_prepare homes it)
+      SlotImg im;
+      uint64_t j = hs >> t.shift;
+      for (uint32_t p = 0; p < t.max_probe; p++, j = (j + 1) & t.mask) {
+        load_img_lo(&t.slots[j], im);
+        const uint32_t tg = im.tag();
+        if (tg == TAG_EMPTY) break;
+        const uint32_t u = im.unit();
+        if (tg < 2 || u < 1 || u > 4 || tg != slot_tag(hs, u) || !img_key_equal(im, key, t.arena)) continue;
+        if (q.dry) {
+          const uint32_t bit = 1u << (j & 31u);
+          if (atomicOr(&q.claim[j >> 5], bit) & bit) continue;
+        } else {
+          if (atomicCAS(&t.slots[j].tag, tg, TAG_TOMB) != tg) continue;
+          t.slots[j].ring = LOG_NONE;
+        }
+        cnt++;
+        v[1] += im.ring() != LOG_NONE;
+        if (key.len > KEY_IN) v[2] += (key.len - KEY_SPLIT + 15) / 16;
+      }
+    }
+    v[0] = cnt;
+    q.removed[i] = cnt;
+  }
+  __shared__ unsigned long long sh[4][3];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const unsigned long long x = wave_sum(v[k]);
+    if (lane == 0) sh[wave][k] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const unsigned long long x = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    if (x) atomicAdd(&q.ctr[threadIdx.x], x);
+  }
+}
+
+// ===========================================================================
 // Diagnostics
 // ===========================================================================
 // Full Redis key stem ‖ strconv.FormatInt((now/div)*div, 10) into a padded
@@ -6116,6 +6183,16 @@ void launch_lookup(const TableDev& t, const HashKey& hk, const Params& P, const 
   b.stem = stem;
   b.stem_cap = b.stem_total = stem_total;
   k_lookup<<<cdiv(q.n, 256), 256, 0, st>>>(t, b, P, time_floor, q);
+}
+
+void launch_forget_keys(const TableDev& t, const HashKey& hk, const uint8_t* stem, uint32_t stem_total,
+                        const ForgetDev& q, hipStream_t st) {
+  if (!q.n) return;
+  BatchDev b{};
+  b.hk = hk;
+  b.stem = stem;
+  b.stem_cap = b.stem_total = stem_total;
+  k_forget_keys<<<cdiv(q.n, 256), 256, 0, st>>>(t, b, q);
 }
 
 bool log_tear_hook() { return RL_LOG_TEAR != 0; }

@@ -780,6 +780,47 @@ class Backend:
             lo = hi
         return out
 
+    # ---- deletion by stem or stem prefix (Redis DEL, SCAN MATCH + DEL)
+    def forget(self, stems: Sequence[bytes], prefix: bool = False, dry_run: bool = False) -> dict:
+        """rl_forget of the stems (prefix=True: of every stem that begins with one
+        of them; at most 64 prefixes of 4096 bytes in all, one call). A stem goes
+        whole: every unit slot, window, history chain and local-cache entry.
+        Keyed stems go in calls of at most max_batch stems and max_stem_bytes
+        bytes. dry_run: select and count only. Returns "removed" (numpy uint32, the
+        slots removed per entry; a prefix's: those not counted under an earlier
+        one) and the rl_forget_info fields summed over the calls. Raises
+        RedisError with the call's status on failure."""
+        n = len(stems)
+        flags = (abi.RL_FORGET_PREFIX if prefix else 0) | (abi.RL_FORGET_DRY_RUN if dry_run else 0)
+        max_n = n if prefix else int(self.cfg.max_batch) or 1 << 20
+        max_b = 1 << 32 if prefix else int(self.cfg.max_stem_bytes) or 128 * max_n
+        off = np.zeros(n + 1, np.int64)
+        if n:
+            off[1:] = np.cumsum([len(s) for s in stems], dtype=np.int64)
+        blob = np.frombuffer(b"".join(stems), np.uint8) if n and off[n] else np.zeros(0, np.uint8)
+        out = {f: 0 for f, _ in abi.RlForgetInfo._fields_}
+        out["removed"] = np.zeros(n, np.uint32)
+        lo = 0
+        while lo < n:
+            hi = min(n, lo + max_n)
+            if int(off[hi]) - int(off[lo]) > max_b:  # the most stems whose bytes fit (one alone: the call says so)
+                hi = max(lo + 1, int(np.searchsorted(off, int(off[lo]) + max_b, side="right")) - 1)
+            sub_off = np.ascontiguousarray(off[lo:hi + 1] - off[lo], np.uint32)
+            sub_stem = np.ascontiguousarray(blob[int(off[lo]):int(off[hi])])
+            if sub_stem.size == 0:
+                sub_stem = np.zeros(1, np.uint8)
+            s = abi.RlStems()
+            s.n, s.flags = hi - lo, flags
+            s.stem_bytes, s.stem_off = abi.ptr(sub_stem), abi.ptr(sub_off)
+            removed = np.zeros(hi - lo, np.uint32)
+            info = abi.RlForgetInfo()
+            self._check(self.L.rl_forget(self.ctx, C.byref(s), abi.ptr(removed), C.byref(info)))
+            out["removed"][lo:hi] = removed
+            for f, _ in abi.RlForgetInfo._fields_:
+                out[f] += int(getattr(info, f))
+            lo = hi
+        return out
+
     # ---- the busiest / the currently blocked keys (redis-cli --hotkeys, SCAN with a filter)
     def hot_keys(self, now: int, k: int, min_count: int = 0, units=None, blocked: bool = False):
         """rl_hot_keys -> (records, info): the k matching records with the largest
@@ -994,6 +1035,26 @@ class GpuRateLimitCache:
         return [HotKey(bytes(blob[int(off[i]):int(off[i + 1])]), int(rec["unit"][i]), int(rec["ws"][i]),
                        int(rec["count"][i]), int(rec["expire"][i]), int(rec["lc"][i]))
                 for i in range(len(rec["ws"]))]
+
+    def forget(self, request, limits=None, dry_run: bool = False) -> dict:
+        """Delete the request's keys (Redis DEL of every window of each, in both
+        stores, and their local-cache entries): the same stems do_limit and peek
+        build (prefix ‖ domain ‖ entries), removed whole, whatever units they were
+        counted under. limits (optional): descriptors with a nil limit are left
+        out, as do_limit leaves them. Returns Backend.forget's dict, "removed"
+        in the order of the descriptors taken."""
+        from .packing import stem_of
+        if limits is not None and len(request.descriptors) != len(limits):
+            raise AssertionError("len(descriptors) != len(limits)")  # base_limiter.go:47
+        stems = [stem_of(self.prefix, request.domain, d.entries) for i, d in enumerate(request.descriptors)
+                 if limits is None or limits[i] is not None]
+        return self.backend.forget(stems, dry_run=dry_run)
+
+    def forget_domain(self, domain: str, dry_run: bool = False) -> dict:
+        """Delete every key of a domain: the stems that begin with
+        cache_key_prefix ‖ domain ‖ '_' (which also begin the keys of a domain
+        named domain ‖ '_' ‖ anything, as a Redis SCAN MATCH would see them)."""
+        return self.backend.forget([(self.prefix + domain + "_").encode()], prefix=True, dry_run=dry_run)
 
     def flush(self):
         """Flush(): nothing is asynchronous on the host path."""
