@@ -1327,6 +1327,91 @@ typedef struct rl_forget_info {  /* 32 bytes */
 int rl_forget(rl_ctx* ctx, const rl_stems* in, uint32_t* removed /* [n] or NULL */,
               rl_forget_info* info /* may be NULL */);
 
+/* ---- List keys by stem prefix, page by page (Redis SCAN MATCH + GET / TTL) -----
+ * rl_scan is the read counterpart of rl_forget's prefix mode: "what does
+ * tenant X hold right now". It selects on the device, returns only the
+ * matching records, and can be resumed where the answer does not fit one
+ * buffer. Like rl_hot_keys it is defined against the export.
+ *
+ * Which keys: a key is one live slot. It is selected when its unit is in
+ * unit_mask (0: every unit) and either n_prefixes == 0 or its stem begins with
+ * one of the prefixes: rl_forget's prefix rule, byte for byte (the stem is at
+ * least as long as the prefix and its first bytes equal the prefix's). A key
+ * is counted under the lowest matching prefix index; with n_prefixes == 0
+ * by_prefix[0] takes everything.
+ *
+ * Which records: a selected key's records are those rl_export_range emits for
+ * its slot, contiguous, oldest window first, count / expire / lc verbatim.
+ * With RL_SCAN_NEWEST only the last of them (the slot's newest window) comes
+ * back and the history log is never walked. With RL_SCAN_LIVE only records
+ * with now <= expire come back (the Redis key exists at q->now). A selected
+ * key without a record left after these filters is no key of the answer: it is
+ * counted nowhere. A key whose chain walk broke carries RL_REC_CHAIN_LOST on
+ * the first record emitted for it (never with RL_SCAN_NEWEST, which does not
+ * walk); info->chains_lost counts such keys.
+ *
+ * One call stays inside one shard. It starts at *cur (all zero: the start) and
+ * covers whole tiles of RL_SCAN_TILE slots, as many consecutive ones as fit
+ * out->n records and out->stem_cap stem bytes (and 2^32 - 1 stem bytes: the
+ * offsets are 32-bit); a shard's last tile may be short. It writes the records
+ * of exactly the covered tiles, sets out->n and stem_off[0..n], and sets *cur
+ * to the first slot not covered; at a shard's end the cursor becomes
+ * {shard + 1, 0}. The scan is complete when cur->shard == n_shards; a call
+ * with that cursor is RL_OK and returns the empty answer (out->n = 0, zero
+ * sums). *info and by_prefix[] describe exactly the records of this call: sums
+ * over the covered tiles. out == NULL covers the rest of the shard and only
+ * counts. A first tile that does not fit gives RL_E_CAPACITY: nothing is
+ * written, *cur is unchanged, and info->need_records / need_stem_bytes say what
+ * that tile alone needs (the other fields of *info are zero but time_floor).
+ *
+ * Determinism: for an unchanged table and query, the concatenation of all
+ * pages is the same byte sequence whatever capacities the calls were given. No
+ * output position comes from an atomic race: positions are per-tile sums and
+ * an in-workgroup scan.
+ *
+ * Cursor guarantee: a key that is in the table from the first page to the last
+ * is returned exactly once (a key never changes its slot). Keys inserted or
+ * evicted between pages may or may not appear. rl_resize and rl_snapshot_load
+ * move keys between slots and so invalidate a cursor; the call cannot detect
+ * that: start again from zero after either.
+ *
+ * Ordering: the call orders after every submitted batch (it completes pending
+ * second halves of the packed and wire paths, host-fed batches and the
+ * progress ring, as rl_export_range does), is synchronous and holds the batch
+ * pipeline for its duration. Strictly read-only, like rl_lookup: no slot, arena
+ * byte, flag, log entry, rl_table_info field or gauge moves.
+ *
+ * Failures, each writing nothing. RL_E_INVALID: a null q or cur; unknown
+ * flags; non-zero reserved fields; a unit_mask bit outside 1..4; bad offsets
+ * (prefix_off[0] != 0, decreasing) or a null prefix array with n_prefixes > 0;
+ * an empty prefix; cur->slot no multiple of RL_SCAN_TILE or beyond the shard;
+ * cur->shard > n_shards; a null array in a non-null out; a ctx that joined a
+ * communicator. RL_E_CAPACITY: more than RL_FORGET_PREFIX_MAX prefixes or more
+ * than RL_FORGET_PREFIX_BYTES bytes of them. RL_E_TIME, with RL_SCAN_LIVE: now
+ * outside [0, 2^32 - 172801] or below the sweep floor. */
+#define RL_SCAN_NEWEST 0x1u   /* only each key's newest window record; the history log is never walked */
+#define RL_SCAN_LIVE   0x2u   /* only records whose Redis key exists at q->now: now <= expire */
+#define RL_SCAN_TILE   1024u  /* a cursor advances in whole tiles of this many slots */
+typedef struct rl_scan_query {
+  uint32_t n_prefixes;          /* 0..RL_FORGET_PREFIX_MAX; 0: every key */
+  uint32_t flags;               /* RL_SCAN_* */
+  const uint8_t* prefix_bytes;  /* <= RL_FORGET_PREFIX_BYTES in all */
+  const uint32_t* prefix_off;   /* n_prefixes + 1, prefix_off[0] == 0 */
+  int64_t now;                  /* read with RL_SCAN_LIVE only */
+  uint32_t unit_mask;           /* bit u (1..4) selects rl_unit u; 0 = every unit */
+  uint32_t reserved;            /* zero */
+} rl_scan_query;
+typedef struct rl_scan_cursor { uint32_t shard, reserved; uint64_t slot; } rl_scan_cursor;  /* start: all zero */
+typedef struct rl_scan_prefix_sum { uint64_t keys, records, hits; } rl_scan_prefix_sum;     /* hits: sum of the records' counts */
+typedef struct rl_scan_info {
+  uint64_t slots_scanned, keys, records, stem_bytes, chains_lost;
+  uint64_t need_records, need_stem_bytes;  /* on RL_E_CAPACITY: what the first tile alone needs */
+  int64_t time_floor;                      /* the ctx's sweep floor */
+} rl_scan_info;
+int rl_scan(rl_ctx* ctx, const rl_scan_query* q, rl_scan_cursor* cur /* in, out */,
+            rl_records* out /* NULL: count only */, rl_scan_prefix_sum* by_prefix /* [max(n_prefixes, 1)] or NULL */,
+            rl_scan_info* info /* may be NULL */);
+
 /* Per-stage device timing (HIP events on the batch stream), for benchmarks.
  * rl_profile(ctx, k) with k >= 1 starts accumulating over every k-th batch,
  * the first sampled one being the k-th submitted after the call (1 = every

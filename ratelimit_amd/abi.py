@@ -287,6 +287,34 @@ class RlForgetInfo(C.Structure):
                 ("arena_bytes", C.c_uint64)]
 
 
+RL_SCAN_NEWEST = 1   # rl_scan_query.flags: only each key's newest window record (the history log is never walked)
+RL_SCAN_LIVE = 2     # only records whose Redis key exists at the query's now: now <= expire
+RL_SCAN_TILE = 1024  # a cursor advances in whole tiles of this many slots
+
+
+class RlScanQuery(C.Structure):
+    """rl_scan_query: which keys and records one rl_scan call selects."""
+    _fields_ = [("n_prefixes", C.c_uint32), ("flags", C.c_uint32), ("prefix_bytes", P), ("prefix_off", P),
+                ("now", C.c_int64), ("unit_mask", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RlScanCursor(C.Structure):
+    """rl_scan_cursor: where the next page starts (all zero: the start; shard == n_shards: done)."""
+    _fields_ = [("shard", C.c_uint32), ("reserved", C.c_uint32), ("slot", C.c_uint64)]
+
+
+class RlScanPrefixSum(C.Structure):
+    """rl_scan_prefix_sum: one page's keys, records and summed counts under one prefix."""
+    _fields_ = [("keys", C.c_uint64), ("records", C.c_uint64), ("hits", C.c_uint64)]
+
+
+class RlScanInfo(C.Structure):
+    """rl_scan_info: sums over the tiles one rl_scan call covered."""
+    _fields_ = [("slots_scanned", C.c_uint64), ("keys", C.c_uint64), ("records", C.c_uint64),
+                ("stem_bytes", C.c_uint64), ("chains_lost", C.c_uint64), ("need_records", C.c_uint64),
+                ("need_stem_bytes", C.c_uint64), ("time_floor", C.c_int64)]
+
+
 RL_MATCH_NONE, RL_MATCH_UNLIMITED, RL_MATCH_LIMIT = 0, 1, 2
 REQUEST_ARRAYS = ("domain_bytes", "domain_off", "now", "hits", "req_idx", "entry_first", "desc_off", "desc_bytes",
                   "key_len", "value_len", "override_flags", "override_rpu", "override_unit", "override_rule")

@@ -988,6 +988,40 @@ int rl_forget(rl_ctx* c, const rl_stems* in, uint32_t* removed, rl_forget_info* 
   return RL_OK;
 }
 
+int rl_scan(rl_ctx* c, const rl_scan_query* q, rl_scan_cursor* cur, rl_records* out, rl_scan_prefix_sum* by_prefix,
+            rl_scan_info* info) {
+  // (a single-shard ctx reports through its engine: rl_last_error reads it there)
+  auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };
+  if (!c || !q || !cur) return bad(RL_E_INVALID, "gpu: null argument");
+  if (c->comm) return bad(RL_E_INVALID, "gpu: rl_scan is not for a ctx that joined a communicator");
+  if (cur->reserved) return bad(RL_E_INVALID, "gpu: rl_scan: cursor's reserved field not zero");
+  if (cur->shard > c->n) return bad(RL_E_INVALID, "gpu: rl_scan: cursor shard beyond n_shards");
+  // the whole call is checked first: a failed call writes nothing
+  if (const int rc = from_engine(c, c->e[0], eng_scan_check(c->e[0], q, out))) return rc;
+  if (cur->shard == c->n) {  // the scan is complete: the empty answer
+    if (cur->slot) return bad(RL_E_INVALID, "gpu: rl_scan: a finished cursor's slot is 0");
+    if (out) {
+      out->n = 0;
+      out->stem_off[0] = 0;
+    }
+    if (by_prefix)
+      for (uint32_t p = 0; p < std::max(q->n_prefixes, 1u); p++) by_prefix[p] = rl_scan_prefix_sum{};
+    if (info) *info = rl_scan_info{};
+    return RL_OK;
+  }
+  if (const int src = settle_local(c)) return src;
+  Engine* e = c->e[cur->shard];
+  uint64_t slot = cur->slot;
+  if (const int rc = from_engine(c, e, eng_scan(e, q, &slot, out, by_prefix, info))) return rc;
+  if (slot >= e->nslots) {
+    cur->shard += 1;
+    cur->slot = 0;
+  } else {
+    cur->slot = slot;
+  }
+  return RL_OK;
+}
+
 int rl_hot_keys(rl_ctx* c, const rl_hot_query* q, rl_records* out, rl_hot_info* info) {
   // (a single-shard ctx reports through its engine: rl_last_error reads it there)
   auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };

@@ -138,6 +138,23 @@ struct Engine {
   uint8_t* arena2 = nullptr;  // compaction target (rl_sweep), swapped with arena
   uint64_t arena_cap16 = 0;
   bool arena_forgotten = false;  // rl_forget removed long stems: the next sweep compacts the arena even if it evicts nothing
+  // rl_scan's device staging, kept across calls and grown on demand (per-call
+  // allocation is what the export pays): the query's prefixes and
+  // per-prefix sums, the span's slot words / tile sums / tile bases, the
+  // records' arrays. scan_span: the largest span in tiles (RL_SCAN_SPAN: tests
+  // cross spans on tiny tables).
+  struct ScanStage {
+    uint8_t* pfx = nullptr;            // RL_FORGET_PREFIX_BYTES
+    uint32_t* poff = nullptr;          // RL_FORGET_PREFIX_MAX + 1
+    unsigned long long* byp = nullptr; // RL_FORGET_PREFIX_MAX x 3, then the error word
+    uint32_t* cnt = nullptr;
+    rlscan::TileSum* sums = nullptr;
+    unsigned long long* base = nullptr;
+    size_t cnt_cap = 0, tile_cap = 0, base_cap = 0;
+    ExportDev o{};
+    size_t rec_cap = 0, byte_cap = 0;
+  } scan;
+  uint32_t scan_span = 4096;
   uint64_t hot_range = 1ull << 22;  // slots per scan range of eng_hot_keys (RL_HOT_RANGE: tests cross ranges on tiny tables)
   // scratch: s[k] per buffer; stripes, counters, time floor, routing and the
   // table-stage error word are shared
@@ -345,6 +362,13 @@ struct HotAnswer {
 };
 int eng_hot_check(Engine* c, const rl_hot_query* q);
 int eng_hot_keys(Engine* c, const rl_hot_query* q, HotAnswer* ans, rl_hot_info* info);
+// rl_scan's checks of the query and the output arrays (host only; eng_scan
+// runs them too), and one call on this engine's table from slot *slot on:
+// *slot becomes the first slot not covered (nslots at the shard's end). out,
+// by_prefix and info may be null.
+int eng_scan_check(Engine* c, const rl_scan_query* q, const rl_records* out);
+int eng_scan(Engine* c, const rl_scan_query* q, uint64_t* slot, rl_records* out, rl_scan_prefix_sum* by_prefix,
+             rl_scan_info* info);
 // rl_forget's whole-call checks against this engine's limits (host only;
 // eng_forget runs them too), and the deletion on this engine's table: keyed
 // stems through the staging of the host-buffer entry points, prefixes by one

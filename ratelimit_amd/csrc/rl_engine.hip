@@ -534,6 +534,8 @@ Engine* eng_create(const rl_config* cfg_in, char* err, size_t errlen) {
   ok = ok && hipHostMalloc((void**)&c->h_list, NBUF * sizeof(uint32_t)) == hipSuccess;
   if (ok) memset(c->h_list, 0, NBUF * sizeof(uint32_t));
   if (const char* uc = getenv("RL_LIST_CUE")) c->list_mode = atoi(uc);  // (A/B knob)
+  if (const char* sp = getenv("RL_SCAN_SPAN"))  // (eng_scan's largest span in tiles, 1 .. 4096)
+    c->scan_span = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(strtoull(sp, nullptr, 0), 1), 4096);
   if (const char* hr = getenv("RL_HOT_RANGE"))  // (eng_hot_keys' scan range in slots, 64 .. 2^22)
     c->hot_range = std::min<uint64_t>(std::max<uint64_t>(strtoull(hr, nullptr, 0), 64), 1ull << 22);
   if (!ok) return fail("gpu: device allocation failed (table_slots/arena/max_batch too large?)", c);
@@ -626,6 +628,11 @@ void eng_destroy(Engine* c) {
   if (c->caller_ready) (void)hipEventDestroy(c->caller_ready);
   if (c->ov_order) (void)hipEventDestroy(c->ov_order);
   for (void* p : {(void*)c->ov.slots, (void*)c->ov.koff, (void*)c->ov.klen, (void*)c->ov.arena, (void*)c->ov.ctr})
+    if (p) (void)hipFree(p);
+  for (void* p : {(void*)c->scan.pfx, (void*)c->scan.poff, (void*)c->scan.byp, (void*)c->scan.cnt, (void*)c->scan.sums,
+                  (void*)c->scan.base, (void*)c->scan.o.stem, (void*)c->scan.o.off, (void*)c->scan.o.unit,
+                  (void*)c->scan.o.flags, (void*)c->scan.o.ws, (void*)c->scan.o.count, (void*)c->scan.o.expire,
+                  (void*)c->scan.o.lc})
     if (p) (void)hipFree(p);
   if (c->h_base) (void)hipHostFree(c->h_base);
   const Scratch& s0 = c->s[0];
@@ -3063,6 +3070,195 @@ int eng_hot_keys(Engine* c, const rl_hot_query* q, HotAnswer* ans, rl_hot_info* 
   HIPCHK(c, hipMemcpyAsync(&h, hs, sizeof h, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   if (h.err || h.cursor != nb) return set_err(c, RL_E_INTERNAL, "gpu: rl_hot_keys gathered other than it sized");
+  return RL_OK;
+}
+
+int eng_scan_check(Engine* c, const rl_scan_query* q, const rl_records* out) {
+  if (!c || !q) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (q->flags & ~(RL_SCAN_NEWEST | RL_SCAN_LIVE)) return set_err(c, RL_E_INVALID, "gpu: rl_scan: unknown flags");
+  if (q->reserved) return set_err(c, RL_E_INVALID, "gpu: rl_scan: reserved field not zero");
+  if (q->unit_mask & ~rlhot::UNIT_BITS) return set_err(c, RL_E_INVALID, "gpu: rl_scan: unit_mask bit outside 1..4");
+  const uint32_t n = q->n_prefixes;
+  if (n > RL_FORGET_PREFIX_MAX) return set_err(c, RL_E_CAPACITY, "gpu: rl_scan: more than RL_FORGET_PREFIX_MAX prefixes");
+  if (n) {
+    if (!q->prefix_bytes || !q->prefix_off) return set_err(c, RL_E_INVALID, "gpu: rl_scan: null prefix array");
+    if (q->prefix_off[0] != 0) return set_err(c, RL_E_INVALID, "gpu: rl_scan prefix offsets must start at 0");
+    for (uint32_t i = 0; i < n; i++)
+      if (q->prefix_off[i + 1] <= q->prefix_off[i])  // (no empty prefix: n_prefixes == 0 is "every key")
+        return set_err(c, RL_E_INVALID, "gpu: rl_scan prefix " + std::to_string(i) + ": empty, or offsets decrease");
+    if (q->prefix_off[n] > RL_FORGET_PREFIX_BYTES)
+      return set_err(c, RL_E_CAPACITY, "gpu: rl_scan: more than RL_FORGET_PREFIX_BYTES bytes of prefixes");
+  }
+  if ((q->flags & RL_SCAN_LIVE) && (q->now < 0 || q->now > (int64_t)NOW_MAX))
+    return set_err(c, RL_E_TIME, "gpu: now out of range");
+  if (out && (!out->stem_off || (out->n && (!out->unit || !out->flags || !out->ws || !out->count || !out->expire ||
+                                            !out->lc)) ||
+              (out->stem_cap && !out->stem_bytes)))
+    return set_err(c, RL_E_INVALID, "gpu: null rl_records array");
+  return RL_OK;
+}
+
+namespace {
+
+// device staging that lives with the engine: at least `need` elements, never shrunk
+template <typename T>
+hipError_t scan_grow(T** p, size_t* cap, size_t need) {
+  if (need <= *cap) return hipSuccess;
+  const size_t want = std::max(need, *cap + *cap / 2);
+  T* q = nullptr;
+  const hipError_t e = dalloc(&q, want);
+  if (e != hipSuccess) return e;
+  if (*p) (void)hipFree(*p);
+  *p = q;
+  *cap = want;
+  return hipSuccess;
+}
+
+}  // namespace
+
+int eng_scan(Engine* c, const rl_scan_query* q, uint64_t* slot, rl_records* out, rl_scan_prefix_sum* by_prefix,
+             rl_scan_info* info) {
+  if (!c || !slot) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  if (const int rc = eng_scan_check(c, q, out)) return rc;
+  if (*slot % RL_SCAN_TILE || *slot > c->nslots)
+    return set_err(c, RL_E_INVALID, "gpu: rl_scan: cursor slot is no multiple of RL_SCAN_TILE, or beyond the shard");
+  RQ_SETTLE(c);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream;
+  HIPCHK(c, after_batches(c, st));  // (the staging below is this synchronous call's own)
+  Engine::ScanStage& S = c->scan;
+  if (!S.pfx) {
+    HIPCHK(c, dalloc(&S.pfx, (size_t)RL_FORGET_PREFIX_BYTES));
+    HIPCHK(c, dalloc(&S.poff, (size_t)RL_FORGET_PREFIX_MAX + 1));
+    HIPCHK(c, dalloc(&S.byp, (size_t)RL_FORGET_PREFIX_MAX * 3 + 1));
+    HIPCHK(c, hipMemsetAsync(S.pfx, 0, RL_FORGET_PREFIX_BYTES, st));
+    HIPCHK(c, hipMemsetAsync(S.poff, 0, (RL_FORGET_PREFIX_MAX + 1) * 4, st));
+  }
+  int64_t floor = 0;
+  HIPCHK(c, hipMemcpyAsync(&floor, c->s[0].time_floor, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if ((q->flags & RL_SCAN_LIVE) && q->now < floor) return set_err(c, RL_E_TIME, "gpu: now below the sweep floor");
+  const uint32_t np = q->n_prefixes, nbins = std::max(np, 1u);
+  if (np) {
+    HIPCHK(c, hipMemcpyAsync(S.pfx, q->prefix_bytes, q->prefix_off[np], hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(S.poff, q->prefix_off, ((size_t)np + 1) * 4, hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(c, hipMemsetAsync(S.byp, 0, ((size_t)RL_FORGET_PREFIX_MAX * 3 + 1) * 8, st));
+  uint32_t* d_err = reinterpret_cast<uint32_t*>(S.byp + RL_FORGET_PREFIX_MAX * 3);
+  const ScanQueryDev dq{S.pfx, S.poff, np, q->flags, (q->flags & RL_SCAN_LIVE) ? (uint32_t)q->now : 0u, q->unit_mask};
+  const TableDev t = table_view(c);
+  const uint64_t total = rlscan::tiles_of(c->nslots), first = *slot / RL_SCAN_TILE;
+  rl_scan_info sum{};
+  sum.time_floor = floor;
+  std::vector<rlscan::TileSum> h_sums;
+  std::vector<uint64_t> h_base;
+  auto slots_of = [&](uint64_t t0, uint64_t t1) {  // slots of the tiles [t0, t1)
+    return std::min(t1 * RL_SCAN_TILE, c->nslots) - std::min(t0 * RL_SCAN_TILE, c->nslots);
+  };
+  uint64_t tile = first;
+  if (!out) {
+    // count only: one pass over the rest of the shard, which it covers whole
+    for (; tile < total;) {
+      const uint32_t nt = (uint32_t)std::min<uint64_t>(total - tile, 1u << 20);
+      HIPCHK(c, scan_grow(&S.sums, &S.tile_cap, nt));
+      launch_scan_count(t, c->nslots, tile, nt, dq, nullptr, S.sums, S.byp, st);
+      HIPCHK(c, hipGetLastError());
+      h_sums.resize(nt);
+      HIPCHK(c, hipMemcpyAsync(h_sums.data(), S.sums, (size_t)nt * sizeof(rlscan::TileSum), hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipStreamSynchronize(st));
+      for (const rlscan::TileSum& x : h_sums) {  // (no cut: a count has no 32-bit offsets to respect)
+        sum.records += x.records;
+        sum.stem_bytes += x.bytes;
+        sum.keys += x.keys;
+        sum.chains_lost += x.lost;
+      }
+      tile += nt;
+    }
+  } else {
+    const uint64_t rec_cap = out->n, byte_cap = std::min<uint64_t>(out->stem_cap, rlscan::BYTES_MAX);
+    // The spans start small and double: a small page then counts a few tiles,
+    // not 2^22 slots, and a large one (the first span: as many tiles as the
+    // page has records per RL_SCAN_TILE) is soon at full width.
+    const uint32_t span0 = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(16, rec_cap / RL_SCAN_TILE), c->scan_span);
+    for (uint32_t span = span0; tile < total; span = std::min(2 * span, c->scan_span)) {
+      const uint32_t nt = (uint32_t)std::min<uint64_t>(total - tile, span);
+      HIPCHK(c, scan_grow(&S.sums, &S.tile_cap, nt));
+      HIPCHK(c, scan_grow(&S.cnt, &S.cnt_cap, (size_t)nt * RL_SCAN_TILE));
+      launch_scan_count(t, c->nslots, tile, nt, dq, S.cnt, S.sums, nullptr, st);
+      HIPCHK(c, hipGetLastError());
+      h_sums.resize(nt);
+      h_base.resize(nt);
+      HIPCHK(c, hipMemcpyAsync(h_sums.data(), S.sums, (size_t)nt * sizeof(rlscan::TileSum), hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipStreamSynchronize(st));
+      const rlscan::Cut cut =
+          rlscan::plan(h_sums.data(), nt, rec_cap - sum.records, byte_cap - sum.stem_bytes, h_base.data());
+      if (!cut.tiles && tile == first) {
+        if (info) {
+          *info = rl_scan_info{};
+          info->need_records = h_sums[0].records;
+          info->need_stem_bytes = h_sums[0].bytes;
+          info->time_floor = floor;
+        }
+        return set_err(c, RL_E_CAPACITY,
+                       "gpu: rl_scan: the first tile holds " + std::to_string(h_sums[0].records) + " records / " +
+                           std::to_string(h_sums[0].bytes) + " stem bytes: larger than rl_records");
+      }
+      if (cut.records) {
+        const uint64_t nrec = cut.records, nb = cut.bytes;
+        HIPCHK(c, scan_grow(&S.base, &S.base_cap, cut.tiles));
+        if (nrec > S.rec_cap) {  // (the seven record arrays grow together)
+          size_t caps[7];
+          for (size_t& x : caps) x = S.rec_cap;
+          HIPCHK(c, scan_grow(&S.o.off, &caps[0], nrec));
+          HIPCHK(c, scan_grow(&S.o.unit, &caps[1], caps[0]));
+          HIPCHK(c, scan_grow(&S.o.flags, &caps[2], caps[0]));
+          HIPCHK(c, scan_grow(&S.o.ws, &caps[3], caps[0]));
+          HIPCHK(c, scan_grow(&S.o.count, &caps[4], caps[0]));
+          HIPCHK(c, scan_grow(&S.o.expire, &caps[5], caps[0]));
+          HIPCHK(c, scan_grow(&S.o.lc, &caps[6], caps[0]));
+          S.rec_cap = caps[0];
+        }
+        HIPCHK(c, scan_grow(&S.o.stem, &S.byte_cap, nb));
+        HIPCHK(c, hipMemcpyAsync(S.base, h_base.data(), (size_t)cut.tiles * 8, hipMemcpyHostToDevice, st));
+        launch_scan_write(t, c->nslots, tile, cut.tiles, dq, S.cnt, S.base, (uint32_t)sum.stem_bytes, S.o, (uint32_t)nrec,
+                          (uint32_t)nb, S.byp, d_err, st);
+        HIPCHK(c, hipGetLastError());
+        const uint64_t r0 = sum.records;
+        HIPCHK(c, hipMemcpyAsync(out->stem_bytes + sum.stem_bytes, S.o.stem, nb, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out->stem_off + r0, S.o.off, nrec * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out->unit + r0, S.o.unit, nrec, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out->flags + r0, S.o.flags, nrec, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out->ws + r0, S.o.ws, nrec * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out->count + r0, S.o.count, nrec * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out->expire + r0, S.o.expire, nrec * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(out->lc + r0, S.o.lc, nrec * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));  // (h_base and the staging are free again)
+      }
+      sum.records += cut.records;
+      sum.stem_bytes += cut.bytes;
+      sum.keys += cut.keys;
+      sum.chains_lost += cut.lost;
+      tile += cut.tiles;
+      if (cut.tiles < nt) break;  // the next tile does not fit: the page is full
+    }
+  }
+  unsigned long long h_byp[RL_FORGET_PREFIX_MAX * 3 + 1] = {};
+  HIPCHK(c, hipMemcpyAsync(h_byp, S.byp, sizeof h_byp, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  uint64_t byp_records = 0;
+  for (uint32_t p = 0; p < nbins; p++) byp_records += h_byp[p * 3 + 1];
+  if ((uint32_t)h_byp[RL_FORGET_PREFIX_MAX * 3] || byp_records != sum.records)
+    return set_err(c, RL_E_INTERNAL, "gpu: rl_scan wrote other than it counted");
+  sum.slots_scanned = slots_of(first, tile);
+  if (out) {
+    out->n = (uint32_t)sum.records;
+    out->stem_off[0] = 0;
+    out->stem_off[sum.records] = (uint32_t)sum.stem_bytes;
+  }
+  if (by_prefix)
+    for (uint32_t p = 0; p < nbins; p++) by_prefix[p] = rl_scan_prefix_sum{h_byp[p * 3], h_byp[p * 3 + 1], h_byp[p * 3 + 2]};
+  if (info) *info = sum;
+  *slot = std::min(tile * RL_SCAN_TILE, c->nslots);
   return RL_OK;
 }
 

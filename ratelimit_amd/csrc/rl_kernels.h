@@ -7,6 +7,7 @@
 
 #include "rl_device.h"
 #include "rl_hot_select.h"
+#include "rl_scan_plan.h"
 #include "rl_tile.h"
 
 namespace rl {
@@ -489,6 +490,30 @@ void launch_forget_keys(const TableDev& t, const HashKey& hk, const uint8_t* ste
 // matches); ctr as ForgetDev's. dry != 0: nothing is written but those.
 void launch_forget_scan(const TableDev& t, uint64_t nslots, const uint8_t* pfx, const uint32_t* poff, uint32_t np,
                         uint32_t dry, unsigned long long* ctr, uint32_t* removed, hipStream_t st);
+// ---- listing by stem prefix, page by page (rl_scan, rl_scan.hip): read-only ----
+// One call's query as the kernels read it. pfx: RL_FORGET_PREFIX_BYTES readable
+// bytes, 16-B aligned, the np <= RL_FORGET_PREFIX_MAX prefixes packed at
+// poff[0..np] (none empty; np == 0: every key). now: read with RL_SCAN_LIVE.
+struct ScanQueryDev {
+  const uint8_t* pfx;
+  const uint32_t* poff;
+  uint32_t np, flags, now, unit_mask;
+};
+// The tiles [tile0, tile0 + ntiles) of RL_SCAN_TILE slots (the shard's last one
+// may be short): sums[k] = tile tile0 + k's records, stem bytes, keys and lost
+// chains after the query's filters, plain stores. cnt (or null): one word per
+// slot of those tiles, for launch_scan_write. byp (or null: left alone):
+// [max(np, 1)][3] words, += keys, records, hits under each prefix.
+void launch_scan_count(const TableDev& t, uint64_t nslots, uint64_t tile0, uint32_t ntiles, const ScanQueryDev& q,
+                       uint32_t* cnt, rlscan::TileSum* sums, unsigned long long* byp, hipStream_t st);
+// The same tiles' records written into o (a staging of rec_cap records and
+// byte_cap stem bytes), tile k at base[k] = records << 32 | bytes relative to
+// o (rlscan::plan); stem offsets are byte0 + the place in o. cnt: what
+// launch_scan_count left for the span that starts at tile0. byp as above.
+// *err |= a lane's records would have left the staging / were not as counted.
+void launch_scan_write(const TableDev& t, uint64_t nslots, uint64_t tile0, uint32_t ntiles, const ScanQueryDev& q,
+                       const uint32_t* cnt, const unsigned long long* base, uint32_t byte0, const ExportDev& o,
+                       uint32_t rec_cap, uint32_t byte_cap, unsigned long long* byp, uint32_t* err, hipStream_t st);
 // ---- the busiest / blocked keys (rl_hot_keys, rl_hot.hip): a read-only scan ----
 // One call's device state (zero at its start).
 struct HotState {

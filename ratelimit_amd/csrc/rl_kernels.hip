@@ -5461,42 +5461,7 @@ __global__ __launch_bounds__(256) void k_resize_relink(const TableDev t, uint64_
 // last one written, the version nearest the head (chains are bounded by the
 // reach rules: a handful of entries).
 // ===========================================================================
-template <typename F>
-__device__ inline bool export_walk(const TableDev& t, uint32_t si, const SlotImg& im, F f) {
-  uint32_t ptr = im.ring(), tprev = im.cur().ws, saved = LOG_NONE, power = 1, lam = 0;
-  for (uint32_t hops = 0; ptr != LOG_NONE; hops++) {
-    const uint32_t pos = ptr & LOG_POS_MASK;
-    if (hops == LOG_MAX_HOPS || pos >= t.log_cap || ptr == saved) return false;
-    if (++lam == power) {
-      saved = ptr;
-      power <<= 1;
-      lam = 0;
-    }
-    const uint4* e = reinterpret_cast<const uint4*>(&t.log[(size_t)(ptr >> LOG_POS_BITS) * t.log_cap + pos]);
-    const uint4 a = e[0], b = e[1];
-    // overwritten (owner, order), or no record of a window below its t_app
-    if (a.x != si || a.y != im.tag() || a.w > tprev || b.x >= a.w) return false;
-    f(Win{b.x, b.y, b.z, b.w});
-    tprev = a.w;
-    ptr = a.z;
-  }
-  return true;
-}
-
-// The newest version of the smallest logged window of slot si above lo (any:
-// the smallest of all). False: none. *lost: the walk broke.
-__device__ inline bool export_next(const TableDev& t, uint32_t si, const SlotImg& im, bool any, uint32_t lo, Win* out,
-                                   bool* lost) {
-  Win best{WS_INVALID, 0, 0, 0};
-  const uint32_t cw = im.cur().ws;
-  *lost = !export_walk(t, si, im, [&](const Win& w) {
-    if (w.ws >= cw) return;  // (cur is the key's newest window)
-    if ((any || w.ws > lo) && w.ws < best.ws) best = w;  // (<: among versions of one window, the first met)
-  });
-  *out = best;
-  return best.ws != WS_INVALID;
-}
-
+// (export_walk / export_next, the chain walk, live in rl_slot_img.h: rl_scan.hip compiles them too.)
 constexpr uint32_t EXPORT_LOST = 0x80000000u;  // k_export_count's per-slot word: records | EXPORT_LOST
 
 // tot: [0] records, [1] stem bytes, [2] keys, [3] chains lost. Grid-stride, the

@@ -1,6 +1,6 @@
 // rl_slot_img.h — device helpers of the table scans that more than one
 // translation unit compiles (rl_kernels.hip: probing, export; rl_hot.hip: the
-// hot-key scan): a slot's whole 64-B sector in registers, a slot's whole stem,
+// hot-key scan; rl_scan.hip: the prefix scan): a slot's whole 64-B sector in registers, a slot's whole stem,
 // a wave's sum.
 #pragma once
 
@@ -62,6 +62,44 @@ __device__ inline void export_stem(const TableDev& t, const Slot* s, uint32_t le
     const uint8_t* ek = t.arena + (size_t)slot_ext(s) * 16;
     for (uint32_t k = KEY_SPLIT; k < len; k++) dst[k] = ek[k - KEY_SPLIT];
   }
+}
+
+// The walk of a slot's history chain that the export and rl_scan share (the
+// checks are described at the export, rl_kernels.hip). False: the walk broke.
+template <typename F>
+__device__ inline bool export_walk(const TableDev& t, uint32_t si, const SlotImg& im, F f) {
+  uint32_t ptr = im.ring(), tprev = im.cur().ws, saved = LOG_NONE, power = 1, lam = 0;
+  for (uint32_t hops = 0; ptr != LOG_NONE; hops++) {
+    const uint32_t pos = ptr & LOG_POS_MASK;
+    if (hops == LOG_MAX_HOPS || pos >= t.log_cap || ptr == saved) return false;
+    if (++lam == power) {
+      saved = ptr;
+      power <<= 1;
+      lam = 0;
+    }
+    const uint4* e = reinterpret_cast<const uint4*>(&t.log[(size_t)(ptr >> LOG_POS_BITS) * t.log_cap + pos]);
+    const uint4 a = e[0], b = e[1];
+    // overwritten (owner, order), or no record of a window below its t_app
+    if (a.x != si || a.y != im.tag() || a.w > tprev || b.x >= a.w) return false;
+    f(Win{b.x, b.y, b.z, b.w});
+    tprev = a.w;
+    ptr = a.z;
+  }
+  return true;
+}
+
+// The newest version of the smallest logged window of slot si above lo (any:
+// the smallest of all). False: none. *lost: the walk broke.
+__device__ inline bool export_next(const TableDev& t, uint32_t si, const SlotImg& im, bool any, uint32_t lo, Win* out,
+                                   bool* lost) {
+  Win best{WS_INVALID, 0, 0, 0};
+  const uint32_t cw = im.cur().ws;
+  *lost = !export_walk(t, si, im, [&](const Win& w) {
+    if (w.ws >= cw) return;  // (cur is the key's newest window)
+    if ((any || w.ws > lo) && w.ws < best.ws) best = w;  // (<: among versions of one window, the first met)
+  });
+  *out = best;
+  return best.ws != WS_INVALID;
 }
 
 }  // namespace rl

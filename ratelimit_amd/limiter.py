@@ -821,6 +821,94 @@ class Backend:
             lo = hi
         return out
 
+    # ---- listing by stem prefix, page by page (Redis SCAN MATCH + GET / TTL)
+    def _scan_query(self, prefixes, units, now, newest):
+        """-> (rl_scan_query, the arrays it points to)."""
+        prefixes = [bytes(p) for p in prefixes]
+        n = len(prefixes)
+        off = np.zeros(n + 1, np.uint32)
+        if n:
+            off[1:] = np.cumsum([len(p) for p in prefixes], dtype=np.int64)
+        blob = np.frombuffer(b"".join(prefixes) or b"\0", np.uint8).copy()
+        q = abi.RlScanQuery()
+        q.n_prefixes = n
+        q.flags = (abi.RL_SCAN_NEWEST if newest else 0) | (abi.RL_SCAN_LIVE if now is not None else 0)
+        q.prefix_bytes, q.prefix_off = abi.ptr(blob), abi.ptr(off)
+        q.now = int(now) if now is not None else 0
+        q.unit_mask = 0
+        for u in (units if units is not None else ()):
+            q.unit_mask |= 1 << int(u)
+        return q, (blob, off)
+
+    def scan(self, prefixes: Sequence[bytes] = (), units=None, now: Optional[int] = None, newest: bool = False,
+             page_records: int = 1 << 16, page_stem_bytes: Optional[int] = None):
+        """rl_scan over every shard, page by page: a generator of (records, info,
+        by_prefix). records: export_range's arrays (fresh ones per page) of the
+        keys whose stem begins with one of `prefixes` (none: every key), a key's
+        records contiguous and oldest first. units: the rl_unit values to select
+        (None: every unit); now: only records live at that clock (RL_SCAN_LIVE);
+        newest: only each key's newest window. info: rl_scan_info as a dict plus
+        "shard" and "cursor" (the (shard, slot) the next page starts at);
+        by_prefix: numpy uint64 [max(len(prefixes), 1), 3] of keys, records,
+        hits. A page holds at most page_records records and page_stem_bytes stem
+        bytes (default 64 per record); where one tile alone needs more
+        (RL_E_CAPACITY) the buffers grow to what info asks and the page is retried
+        once. Raises RedisError with the call's status otherwise."""
+        q, keep = self._scan_query(prefixes, units, now, newest)
+        nbins = max(int(q.n_prefixes), 1)
+        cur = abi.RlScanCursor()
+        n_cap = int(page_records)
+        stem_cap = int(page_stem_bytes) if page_stem_bytes is not None else 64 * max(n_cap, 1)
+        n_shards = self.n_shards()
+        while cur.shard < n_shards:
+            info = abi.RlScanInfo()
+            byp = np.zeros((nbins, 3), np.uint64)
+            shard = int(cur.shard)
+            for attempt in (0, 1):
+                bufs = {}
+                self._export_alloc(bufs, n_cap, stem_cap)
+                r = abi.RlRecords()
+                r.n, r.stem_cap = n_cap, stem_cap
+                for k in ("stem_bytes", "stem_off") + tuple(abi.RECORD_DTYPES):
+                    setattr(r, k, abi.ptr(bufs[k]))
+                rc = self.L.rl_scan(self.ctx, C.byref(q), C.byref(cur), C.byref(r), abi.ptr(byp), C.byref(info))
+                if rc == abi.RL_E_CAPACITY and attempt == 0 and (info.need_records or info.need_stem_bytes):
+                    n_cap = max(n_cap, int(info.need_records))
+                    stem_cap = max(stem_cap, int(info.need_stem_bytes))
+                    continue
+                self._check(rc)
+                break
+            n = r.n
+            rec = {k: bufs[k][:n] for k in abi.RECORD_DTYPES}
+            rec["stem_off"] = bufs["stem_off"][:n + 1]
+            rec["stem_bytes"] = bufs["stem_bytes"][:int(bufs["stem_off"][n])]
+            d = {f: getattr(info, f) for f, _ in abi.RlScanInfo._fields_}
+            d["shard"], d["cursor"] = shard, (int(cur.shard), int(cur.slot))
+            yield rec, d, byp
+        del keep
+
+    def count_keys(self, prefixes: Sequence[bytes] = (), units=None, now: Optional[int] = None,
+                   newest: bool = False) -> dict:
+        """rl_scan's count-only form summed over the shards: the rl_scan_info sums
+        (slots_scanned, keys, records, stem_bytes, chains_lost) and "by_prefix"
+        (numpy uint64 [max(len(prefixes), 1), 3]: keys, records, hits). Nothing
+        but the sums crosses to the host."""
+        q, keep = self._scan_query(prefixes, units, now, newest)
+        nbins = max(int(q.n_prefixes), 1)
+        out = {f: 0 for f in ("slots_scanned", "keys", "records", "stem_bytes", "chains_lost")}
+        out["by_prefix"] = np.zeros((nbins, 3), np.uint64)
+        cur = abi.RlScanCursor()
+        n_shards = self.n_shards()
+        while cur.shard < n_shards:
+            info = abi.RlScanInfo()
+            byp = np.zeros((nbins, 3), np.uint64)
+            self._check(self.L.rl_scan(self.ctx, C.byref(q), C.byref(cur), None, abi.ptr(byp), C.byref(info)))
+            for f in ("slots_scanned", "keys", "records", "stem_bytes", "chains_lost"):
+                out[f] += int(getattr(info, f))
+            out["by_prefix"] += byp
+        del keep
+        return out
+
     # ---- the busiest / the currently blocked keys (redis-cli --hotkeys, SCAN with a filter)
     def hot_keys(self, now: int, k: int, min_count: int = 0, units=None, blocked: bool = False):
         """rl_hot_keys -> (records, info): the k matching records with the largest
@@ -1055,6 +1143,25 @@ class GpuRateLimitCache:
         cache_key_prefix ‖ domain ‖ '_' (which also begin the keys of a domain
         named domain ‖ '_' ‖ anything, as a Redis SCAN MATCH would see them)."""
         return self.backend.forget([(self.prefix + domain + "_").encode()], prefix=True, dry_run=dry_run)
+
+    def list_keys(self, domain: str, entries=(), live: bool = True, newest: bool = True) -> list:
+        """The keys a domain (or, with entries, a descriptor prefix of it) holds:
+        a list of HotKey(stem, unit, ws, count, expire, lc), one per window record,
+        a key's records contiguous and oldest first. The stem prefix is
+        forget_domain's, cache_key_prefix ‖ domain ‖ '_' (with entries: stem_of's
+        stem, which also begins the stems of longer descriptors); live: only
+        records whose Redis key exists at the time source's now; newest: only
+        each key's newest window."""
+        from .packing import stem_of
+        prefix = stem_of(self.prefix, domain, entries) if entries else (self.prefix + domain + "_").encode()
+        now = self.time_source.unix_now() if live else None
+        out = []
+        for rec, _, _ in self.backend.scan([prefix], now=now, newest=newest):
+            off, blob = rec["stem_off"], rec["stem_bytes"]
+            out += [HotKey(bytes(blob[int(off[i]):int(off[i + 1])]), int(rec["unit"][i]), int(rec["ws"][i]),
+                           int(rec["count"][i]), int(rec["expire"][i]), int(rec["lc"][i]))
+                    for i in range(len(rec["ws"]))]
+        return out
 
     def flush(self):
         """Flush(): nothing is asynchronous on the host path."""
