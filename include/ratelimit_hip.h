@@ -1249,6 +1249,86 @@ typedef struct rl_resize_info {
 } rl_resize_info;
 int rl_resize(rl_ctx* ctx, uint64_t table_slots, rl_resize_info* info /* may be NULL */);
 
+/* ---- Resize the history log in place ------------------------------------------
+ * rl_resize_history rebuilds every shard's history log at another size, on the
+ * device, from the live chains only: the answer to a growing
+ * rl_table_info.history_lost or history_refused ("size history_entries up")
+ * that needs no second ctx, the way to give the log's memory back, and the
+ * log's only cleaner (rl_sweep and rl_forget leave a dead key's entries to be
+ * overwritten; a ring full of unreachable entries wraps onto live ones just as
+ * soon as a full one).
+ *
+ * Size: history_entries is rounded exactly as rl_create rounds it: per
+ * partition (64 of them) a power of two, at least max(history_entries / 64,
+ * max_batch / 16, 1024) and at most 2^25. 0, or more than 2^31, is
+ * RL_E_INVALID. The new size may be larger than, smaller than or equal to the
+ * current one; equal is a compaction that drops every unreachable entry, as an
+ * equal rl_resize drops every tombstone.
+ *
+ * Ordering: as rl_resize. The call orders after every submitted batch, is
+ * synchronous and holds the batch pipeline for its duration. RL_E_INVALID on a
+ * ctx that joined a communicator.
+ *
+ * Preserved: for every live key with a chain, the entries that a lookup's walk
+ * accepts from the chain's head (owner slot and tag, non-increasing append
+ * time, a position inside its partition, no cycle, at most 65536 hops) are
+ * copied, window records verbatim, every version of every window, in the same
+ * order. A chain that ended cleanly ends cleanly; a chain that the log had cut
+ * (an overwritten entry, a refused append) ends in the same place and its
+ * lookups keep answering RL_E_TIME, a key whose head entry itself was lost
+ * included. So every rl_do_limit*, rl_lookup, rl_export_range, rl_scan and
+ * rl_sweep afterwards sees the same records for every key and ends the same
+ * way: no answer changes. Entries that no live chain reaches are gone.
+ * Untouched: the table, the arena, history_lost / _refused, the sweep floor,
+ * the gauges, batches, decisions, the config and the hash key;
+ * rl_table_info.history_appended does not drop. After success
+ * rl_table_info.history_entries is the new size, rl_snapshot_size follows it,
+ * and a snapshot of the ctx loads into a fresh ctx created with the new
+ * history_entries (a snapshot taken before the call is refused, as any
+ * snapshot of another log geometry is).
+ *
+ * A failed call leaves the ctx exactly as it was (the same log bytes, the same
+ * slots, the same info):
+ *   RL_E_CAPACITY  some partition of the new log was asked for more entries
+ *                  than it holds (found by the placement on the device, which
+ *                  never writes past a partition): choose a larger size;
+ *   RL_E_HIP       the new log cannot be allocated: the old log, the new log
+ *                  and 4 bytes per table slot coexist during the call.
+ * The slots' chain heads are stored only after every shard has placed. (A
+ * device failure after that point, which no input can cause, is RL_E_HIP and
+ * leaves the ctx unusable, like any failed kernel.)
+ *
+ * Multi-shard ctx: every shard rebuilds its log at history_entries on its own
+ * device, concurrently; no shard changes unless all placed. *info (optional)
+ * is summed over the shards, longest_chain and fill_max the maxima. */
+typedef struct rl_history_resize_info {
+  uint64_t entries_before, entries_after;  /* the log's capacity: summed over shards */
+  uint64_t written_before;                 /* entries the old log held: sum of min(append counter, partition size) */
+  uint64_t entries_kept;                   /* entries copied: those on live keys' chains */
+  uint64_t entries_dropped;                /* written_before - entries_kept */
+  uint64_t chains;                         /* live keys with a chain */
+  uint64_t chains_lost;                    /* of them, chains that end in a lost entry afterwards (as before) */
+  uint64_t fill_max;                       /* most entries placed in one partition (of entries_after / 64 per shard) */
+  uint32_t longest_chain;                  /* entries */
+  uint32_t reserved;
+} rl_history_resize_info;
+int rl_resize_history(rl_ctx* ctx, uint64_t history_entries, rl_history_resize_info* info /* may be NULL */);
+
+/* ---- Resize the long-stem arena in place --------------------------------------
+ * rl_resize_arena gives every shard a long-stem arena (and the spare one that
+ * rl_sweep compacts into) of arena_bytes: the answer to RL_E_ARENA_FULL that
+ * needs no second ctx, and the way to give the arena's memory back.
+ * arena_bytes must be a non-zero multiple of 16 of at most 2^36 (slots store
+ * 32-bit offsets in 16-B units), else RL_E_INVALID; and at least the bytes in
+ * use (rl_table_info.arena_bytes_used), else RL_E_ARENA_FULL and nothing
+ * changes: run rl_sweep first, it compacts. The used bytes are copied device
+ * to device and offsets do not change, so no slot is touched. Ordering as
+ * rl_resize; the old and the new pair of arenas coexist during the call
+ * (RL_E_HIP if the new pair cannot be allocated, the ctx as it was).
+ * Multi-shard ctx: every shard does this, all or none. RL_E_INVALID on a ctx
+ * that joined a communicator. */
+int rl_resize_arena(rl_ctx* ctx, uint64_t arena_bytes);
+
 /* ---- Delete keys by stem or by stem prefix (Redis DEL, SCAN MATCH + DEL) ------
  * rl_forget removes stems from the table on the device: the tenant that a
  * misconfigured limit blocked, the old window's count after a limit was

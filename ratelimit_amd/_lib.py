@@ -25,7 +25,7 @@ EXPORTS = ["rl_abi_version", "rl_create", "rl_destroy", "rl_last_error", "rl_do_
            "rl_debug_verdict", "rl_request_batch_pack", "rl_do_limit_requests_packed_async",
            "rl_do_limit_wire_async", "rl_response_bound", "rl_do_limit_wire_respond_async", "rl_response_serialize",
            "rl_debug_respond", "rl_hot_keys", "rl_resize", "rl_override_rules_enable", "rl_override_rules_info_get",
-           "rl_override_rule_keys", "rl_forget", "rl_scan"]
+           "rl_override_rule_keys", "rl_forget", "rl_scan", "rl_resize_history", "rl_resize_arena"]
 
 _libs = {}
 
@@ -165,6 +165,9 @@ def load(path):
     if hasattr(L, "rl_scan"):  # (A/B runs load the parent's library)
         L.rl_scan.argtypes = [C.c_void_p, C.POINTER(abi.RlScanQuery), C.POINTER(abi.RlScanCursor),
                               C.POINTER(abi.RlRecords), C.c_void_p, C.POINTER(abi.RlScanInfo)]
+    if hasattr(L, "rl_resize_history"):  # (A/B runs load the parent's library)
+        L.rl_resize_history.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(abi.RlHistoryResizeInfo)]
+        L.rl_resize_arena.argtypes = [C.c_void_p, C.c_uint64]
     if L.rl_abi_version() != abi.ABI_VERSION:
         raise RuntimeError("libratelimit_hip.so ABI mismatch")
     _libs[path] = L

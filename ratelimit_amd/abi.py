@@ -270,6 +270,15 @@ class RlResizeInfo(C.Structure):
                 ("longest_probe", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class RlHistoryResizeInfo(C.Structure):
+    """rl_history_resize_info: what one rl_resize_history kept and dropped (summed over
+    shards; longest_chain and fill_max the maxima)."""
+    _fields_ = [("entries_before", C.c_uint64), ("entries_after", C.c_uint64), ("written_before", C.c_uint64),
+                ("entries_kept", C.c_uint64), ("entries_dropped", C.c_uint64), ("chains", C.c_uint64),
+                ("chains_lost", C.c_uint64), ("fill_max", C.c_uint64), ("longest_chain", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 RL_FORGET_PREFIX = 1   # rl_stems.flags: every entry is a stem prefix, not a whole stem
 RL_FORGET_DRY_RUN = 2  # select and count, change nothing
 RL_FORGET_PREFIX_MAX = 64      # prefixes per call

@@ -49,7 +49,7 @@ constexpr uint32_t MAX_LOCAL_SHARDS = 16;
 
 // One shard's worker: runs its router's collective steps on its own thread.
 struct ShardWorker {
-  enum Job { IDLE, BATCH, SYNC, RESIZE, FORGET, EXIT };
+  enum Job { IDLE, BATCH, SYNC, RESIZE, FORGET, RELOG, EXIT };
   std::thread th;
   std::mutex mu;
   std::condition_variable cv;
@@ -60,6 +60,8 @@ struct ShardWorker {
   hipStream_t caller = nullptr;
   uint64_t rs_slots = 0;  // RESIZE: the new slot count, and what the shard placed
   ResizePlan rs_plan;
+  uint64_t rl_entries = 0;  // RELOG: the new history_entries, and what the shard placed
+  RelogPlan rl_plan;
   const rl_stems* fg_in = nullptr;  // FORGET: the call's prefixes, and this shard's answer
   uint32_t fg_removed[RL_FORGET_PREFIX_MAX] = {};
   rl_forget_info fg_info{};
@@ -136,6 +138,8 @@ void worker_main(rl_ctx* c, uint32_t j) {
       rc = comm_do_limit(c->r[j], c->e[j], &w.in, &w.out, w.caller, &w.io);
     } else if (job == ShardWorker::RESIZE) {  // (the placement only: rl_resize commits once every shard has placed)
       rc = eng_resize_place(c->e[j], w.rs_slots, &w.rs_plan);
+    } else if (job == ShardWorker::RELOG) {  // (likewise: rl_resize_history commits once every shard has placed)
+      rc = eng_relog_place(c->e[j], w.rl_entries, &w.rl_plan);
     } else if (job == ShardWorker::FORGET) {  // (prefix mode: every shard scans its own table)
       rc = eng_forget(c->e[j], w.fg_in, w.fg_removed, &w.fg_info);
     } else {  // SYNC: the pending batch (collective), the router's streams, then the engine's error words
@@ -816,6 +820,68 @@ int rl_resize(rl_ctx* c, uint64_t table_slots, rl_resize_info* info) {
   if (rc) return rc;
   c->cfg.table_slots = table_slots;
   if (info) *info = sum;
+  return RL_OK;
+}
+
+int rl_resize_history(rl_ctx* c, uint64_t history_entries, rl_history_resize_info* info) {
+  // (a single-shard ctx reports through its engine: rl_last_error reads it there)
+  auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };
+  if (!c) return bad(RL_E_INVALID, "gpu: null ctx");
+  if (c->comm) return bad(RL_E_INVALID, "gpu: rl_resize_history is not for a ctx that joined a communicator");
+  if (const int rc = from_engine(c, c->e[0], eng_relog_check(c->e[0], history_entries))) return rc;
+  if (c->n == 1) {
+    const int rc = eng_resize_history(c->e[0], history_entries, info);
+    if (!rc) c->cfg.history_entries = c->e[0]->cfg.history_entries;
+    return rc;
+  }
+  if (const int src = settle_local(c)) return src;
+  // every shard copies its live chains into a new log on its own device and
+  // worker; nothing of any shard has changed until all of them have succeeded
+  for (uint32_t j = 0; j < c->n; j++) c->w[j].rl_entries = history_entries;
+  int rc = run_shards(c, ShardWorker::RELOG);
+  rl_history_resize_info sum{};
+  for (uint32_t j = 0; j < c->n && !rc; j++) {
+    rc = from_engine(c, c->e[j], eng_relog_commit(c->e[j], &c->w[j].rl_plan));
+    const rl_history_resize_info& x = c->w[j].rl_plan.info;
+    sum.entries_before += x.entries_before;
+    sum.entries_after += x.entries_after;
+    sum.written_before += x.written_before;
+    sum.entries_kept += x.entries_kept;
+    sum.entries_dropped += x.entries_dropped;
+    sum.chains += x.chains;
+    sum.chains_lost += x.chains_lost;
+    sum.fill_max = std::max(sum.fill_max, x.fill_max);
+    sum.longest_chain = std::max(sum.longest_chain, x.longest_chain);
+  }
+  for (uint32_t j = 0; j < c->n; j++) eng_relog_abort(c->e[j], &c->w[j].rl_plan);  // (what was not committed)
+  if (rc) return rc;
+  c->cfg.history_entries = c->e[0]->cfg.history_entries;
+  if (info) *info = sum;
+  return RL_OK;
+}
+
+int rl_resize_arena(rl_ctx* c, uint64_t arena_bytes) {
+  auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };
+  if (!c) return bad(RL_E_INVALID, "gpu: null ctx");
+  if (c->comm) return bad(RL_E_INVALID, "gpu: rl_resize_arena is not for a ctx that joined a communicator");
+  if (const int rc = from_engine(c, c->e[0], eng_arena_check(c->e[0], arena_bytes))) return rc;
+  if (c->n == 1) {
+    const int rc = eng_resize_arena(c->e[0], arena_bytes);
+    if (!rc) c->cfg.arena_bytes = arena_bytes;
+    return rc;
+  }
+  if (const int src = settle_local(c)) return src;
+  // every shard gets its new pair and copy first (small: no worker job); no
+  // shard swaps unless all of them have
+  ArenaPlan plan[MAX_LOCAL_SHARDS];
+  int rc = RL_OK;
+  for (uint32_t j = 0; j < c->n && !rc; j++) rc = from_engine(c, c->e[j], eng_arena_place(c->e[j], arena_bytes, &plan[j]));
+  for (uint32_t j = 0; j < c->n; j++) {
+    if (!rc) eng_arena_commit(c->e[j], &plan[j]);
+    else eng_arena_abort(c->e[j], &plan[j]);
+  }
+  if (rc) return rc;
+  c->cfg.arena_bytes = arena_bytes;
   return RL_OK;
 }
 

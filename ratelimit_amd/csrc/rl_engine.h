@@ -123,6 +123,9 @@ struct Engine {
   uint32_t log_cap = 0;
   unsigned long long* log_ctr = nullptr;
   uint32_t horizon = 0;
+  // appends that the counters no longer show: rl_resize_history restarts them
+  // at the entries it placed, and rl_table_info.history_appended must not drop
+  uint64_t hist_base = 0;
   uint32_t* tear = nullptr;  // rl_debug_log_tear's armed state (device; RL_LOG_TEAR builds)
   // RL_DEBUG_COPYTIME: host-fed input copies timed with events (stderr at destroy)
   bool copy_time = false;
@@ -393,6 +396,37 @@ int eng_resize_place(Engine* c, uint64_t table_slots, ResizePlan* p);
 int eng_resize_commit(Engine* c, ResizePlan* p);
 void eng_resize_abort(Engine* c, ResizePlan* p);
 int eng_resize(Engine* c, uint64_t table_slots, rl_resize_info* info);
+// rl_resize_history on this engine, in rl_resize's two steps.
+// eng_relog_place copies the entries on live chains into a new log beside the
+// old one and changes nothing of the engine (any failure leaves the plan
+// empty); once every shard has placed, eng_relog_commit stores the new chain
+// heads, sets the append counters, swaps the logs and frees the old one, else
+// eng_relog_abort frees what was placed. eng_relog_check: the size alone.
+struct RelogPlan {
+  LogEnt* log = nullptr;              // the new log (after the commit's swap: the old one)
+  uint32_t* map = nullptr;            // [nslots] new chain head of each live slot with a chain
+  unsigned long long* ctr = nullptr;  // [RELOG_CTR_WORDS]
+  uint32_t log_cap = 0;
+  std::vector<unsigned long long> fill;  // [LOG_PARTS] entries placed per partition (the new append counters)
+  uint64_t appended = 0;                 // the old append counters' sum
+  rl_history_resize_info info{};
+};
+int eng_relog_check(Engine* c, uint64_t history_entries);
+int eng_relog_place(Engine* c, uint64_t history_entries, RelogPlan* p);
+int eng_relog_commit(Engine* c, RelogPlan* p);
+void eng_relog_abort(Engine* c, RelogPlan* p);
+int eng_resize_history(Engine* c, uint64_t history_entries, rl_history_resize_info* info);
+// rl_resize_arena on this engine, likewise: eng_arena_place allocates the new
+// pair and copies the used bytes, eng_arena_commit swaps and frees the old pair.
+struct ArenaPlan {
+  uint8_t *arena = nullptr, *arena2 = nullptr;
+  uint64_t cap16 = 0;
+};
+int eng_arena_check(Engine* c, uint64_t arena_bytes);
+int eng_arena_place(Engine* c, uint64_t arena_bytes, ArenaPlan* p);
+void eng_arena_commit(Engine* c, ArenaPlan* p);
+void eng_arena_abort(Engine* c, ArenaPlan* p);
+int eng_resize_arena(Engine* c, uint64_t arena_bytes);
 
 // Owner side of a routed batch, pipelined on the engine's streams like
 // eng_do_limit_async: unpack the n received wire records (chunks of n_src

@@ -25,6 +25,7 @@
 #include "../../include/ratelimit_hip.h"
 #include "rl_device.h"
 #include "rl_kernels.h"
+#include "rl_log_geom.h"
 #include "rl_match.h"
 #include "rl_engine.h"
 
@@ -433,7 +434,7 @@ Engine* eng_create(const rl_config* cfg_in, char* err, size_t errlen) {
   if (cfg.table_slots & (cfg.table_slots - 1)) return fail("gpu: table_slots must be a power of two", nullptr);
   if (!cfg.arena_bytes) cfg.arena_bytes = 64ull << 20;
   if (!cfg.history_entries) cfg.history_entries = cfg.table_slots;
-  if (cfg.history_entries > (uint64_t)LOG_PARTS * LOG_PART_MAX)
+  if (!log_entries_fit(cfg.history_entries, LOG_PARTS, LOG_PART_MAX))
     return fail("gpu: history_entries must be at most 2^31", nullptr);
   if (cfg.expiration_jitter_max_seconds < 0) return fail("gpu: expiration_jitter_max_seconds must be >= 0", nullptr);
   if (!cfg.max_batch) cfg.max_batch = 1u << 20;
@@ -455,16 +456,8 @@ Engine* eng_create(const rl_config* cfg_in, char* err, size_t errlen) {
   c->hk = hash_key_of(c->hash_seed, cfg.debug_hash_bits);
   c->nslots = cfg.table_slots;
   {
-    // per partition a power of two, and at least 1/16 of a batch. A batch's
-    // appends are spread over the partitions by workgroup and wave, but a
-    // skewed one (a hot key replayed serially, the exact path's 8 workgroups)
-    // can send more than that to one partition: log_append then refuses the
-    // excess (rl_table_info.history_refused; those windows' later lookups are
-    // RL_E_TIME) rather than wrap onto entries of the same batch
-    const uint64_t want = std::max<uint64_t>(cfg.history_entries / LOG_PARTS, std::max<uint64_t>(cfg.max_batch / 16, 1024));
-    uint64_t cap = 1;
-    while (cap * 2 <= want && cap * 2 <= LOG_PART_MAX) cap *= 2;
-    if (cap < want && cap < LOG_PART_MAX) cap *= 2;
+    // per partition a power of two, and at least 1/16 of a batch (rl_log_geom.h)
+    const uint64_t cap = log_part_cap(cfg.history_entries, cfg.max_batch, LOG_PARTS, LOG_PART_MAX);
     c->log_cap = (uint32_t)cap;
     c->cfg.history_entries = (uint64_t)LOG_PARTS * cap;
     c->horizon = (uint32_t)std::min<int64_t>(cfg.expiration_jitter_max_seconds, 1ll << 30);
@@ -1411,7 +1404,7 @@ int eng_table_info_get(Engine* c, rl_table_info* info) {
   unsigned long long lost = 0, refused = 0;
   HIPCHK(c, log_ctr_get(c, ctr, &lost, &refused));  // (synchronises: h_counters is read below)
   info->history_entries = (uint64_t)LOG_PARTS * c->log_cap;
-  info->history_appended = 0;
+  info->history_appended = c->hist_base;  // (what rl_resize_history took off the counters)
   for (unsigned long long k : ctr) info->history_appended += k;
   info->history_lost = lost;
   info->history_refused = refused;
@@ -2889,6 +2882,7 @@ int eng_snapshot_load(Engine* c, const void* host, uint64_t bytes) {
   std::vector<unsigned long long> hc((size_t)(LOG_PARTS + 1) * LOG_CTR_STRIDE, 0ull);
   for (uint32_t k = 0; k < LOG_PARTS; k++) hc[(size_t)k * LOG_CTR_STRIDE] = ctr[k];
   HIPCHK(c, hipMemcpy(c->log_ctr, hc.data(), hc.size() * 8, hipMemcpyHostToDevice));
+  c->hist_base = 0;  // (the counters are the snapshot's)
   if (h.arena_used16) HIPCHK(c, hipMemcpy(c->arena, p, h.arena_used16 * 16, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->s[0].counters + 4, &h.arena_used16, 8, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->s[0].time_floor, &h.time_floor, 8, hipMemcpyHostToDevice));
@@ -3579,6 +3573,191 @@ int eng_resize(Engine* c, uint64_t table_slots, rl_resize_info* info) {
   if (const int rc = eng_resize_place(c, table_slots, &p)) return rc;
   if (const int rc = eng_resize_commit(c, &p)) return rc;
   if (info) *info = p.info;
+  return RL_OK;
+}
+
+// ---------------------------------------------------------------------------
+// rl_resize_history on one engine, in rl_resize's two steps. eng_relog_place
+// drains the pipeline, allocates the new log and the head map and runs the
+// placement, which only reads the table and the old log: whatever it returns
+// but RL_OK, the engine is as it was and the plan is empty. eng_relog_commit
+// stores the new chain heads into the slots (the one step that writes shared
+// state in place), restarts the append counters at the entries placed (the
+// log_ctr allocation stays: k_b_begin reads it; its line of lost / refused
+// counts is left alone), swaps log / log_cap and frees the old log;
+// eng_relog_abort drops a placed plan instead.
+// ---------------------------------------------------------------------------
+void eng_relog_abort(Engine* c, RelogPlan* p) {
+  if (!p) return;
+  if (c && (p->log || p->map || p->ctr)) (void)hipSetDevice(c->cfg.device);
+  if (p->log) (void)hipFree(p->log);
+  if (p->map) (void)hipFree(p->map);
+  if (p->ctr) (void)hipFree(p->ctr);
+  *p = RelogPlan{};
+}
+
+int eng_relog_check(Engine* c, uint64_t history_entries) {
+  if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
+  if (!history_entries || !log_entries_fit(history_entries, LOG_PARTS, LOG_PART_MAX))
+    return set_err(c, RL_E_INVALID, "gpu: rl_resize_history: history_entries must be in [1, 2^31]");
+  return RL_OK;
+}
+
+int eng_relog_place(Engine* c, uint64_t history_entries, RelogPlan* p) {
+  if (!p) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  *p = RelogPlan{};
+  if (const int rc = eng_relog_check(c, history_entries)) return rc;
+  RQ_SETTLE(c);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream;
+  HIPCHK(c, after_batches(c, st));
+  const uint32_t cap = (uint32_t)log_part_cap(history_entries, c->cfg.max_batch, LOG_PARTS, LOG_PART_MAX);
+  std::vector<unsigned long long> old;
+  HIPCHK(c, log_ctr_get(c, old, nullptr));
+  hipError_t e = dalloc(&p->log, (size_t)LOG_PARTS * cap);
+  if (e == hipSuccess) e = dalloc(&p->map, c->nslots);
+  if (e == hipSuccess) e = dalloc(&p->ctr, RELOG_CTR_WORDS);
+  // (the new log is not cleared: entries are written before any chain points at them, as at rl_create)
+  if (e == hipSuccess) e = hipMemsetAsync(p->ctr, 0, RELOG_CTR_WORDS * 8, st);
+  std::vector<unsigned long long> h(RELOG_CTR_WORDS);
+  if (e == hipSuccess) {
+    launch_relog_place(table_view(c), c->nslots, p->log, cap, p->map, p->ctr, st);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h.data(), p->ctr, h.size() * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();  // (an allocation that failed is this call's error, not the next one's)
+    eng_relog_abort(c, p);
+    return set_err(c, RL_E_HIP, std::string("gpu: rl_resize_history: ") + hipGetErrorString(e) +
+                                    " (the old log, the new log and 4 bytes per slot coexist during the call)");
+  }
+  const unsigned long long* stats = h.data() + RELOG_CTR_STATS;
+  uint64_t fill_max = 0;
+  p->fill.resize(LOG_PARTS);
+  for (uint32_t k = 0; k < LOG_PARTS; k++) {
+    p->fill[k] = h[(size_t)k * LOG_CTR_STRIDE];
+    fill_max = std::max<uint64_t>(fill_max, p->fill[k]);
+  }
+  if (stats[4] || fill_max > cap) {
+    eng_relog_abort(c, p);
+    return set_err(c, RL_E_CAPACITY, "gpu: rl_resize_history: a partition of the new log was asked for " +
+                                         std::to_string(fill_max) + " entries and holds " + std::to_string(cap) +
+                                         " (history_entries of at least " + std::to_string(fill_max * LOG_PARTS) +
+                                         " would fit)");
+  }
+  p->log_cap = cap;
+  p->info.entries_before = (uint64_t)LOG_PARTS * c->log_cap;
+  p->info.entries_after = (uint64_t)LOG_PARTS * cap;
+  for (unsigned long long k : old) {
+    p->appended += k;
+    p->info.written_before += std::min<uint64_t>(k, c->log_cap);
+  }
+  p->info.entries_kept = stats[1];
+  p->info.entries_dropped = p->info.written_before - stats[1];
+  p->info.chains = stats[0];
+  p->info.chains_lost = stats[2];
+  p->info.longest_chain = (uint32_t)stats[3];
+  p->info.fill_max = fill_max;
+  return RL_OK;
+}
+
+int eng_relog_commit(Engine* c, RelogPlan* p) {
+  if (!c || !p || !p->log) return set_err(c, RL_E_INVALID, "gpu: rl_resize_history: nothing placed");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream;
+  std::vector<unsigned long long> hc((size_t)LOG_PARTS * LOG_CTR_STRIDE, 0ull);
+  uint64_t placed = 0;
+  for (uint32_t k = 0; k < LOG_PARTS; k++) {
+    hc[(size_t)k * LOG_CTR_STRIDE] = p->fill[k];
+    placed += p->fill[k];
+  }
+  launch_relog_commit(c->slots, c->nslots, p->map, st);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(c->log_ctr, hc.data(), hc.size() * 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {  // (a failed kernel: the device's state is lost either way)
+    eng_relog_abort(c, p);
+    return set_err(c, RL_E_HIP, std::string("gpu: rl_resize_history: commit: ") + hipGetErrorString(e));
+  }
+  c->hist_base += p->appended - placed;  // (history_appended stays where it was)
+  std::swap(c->log, p->log);  // (the plan now holds the old log: freed below)
+  c->log_cap = p->log_cap;
+  c->cfg.history_entries = (uint64_t)LOG_PARTS * p->log_cap;
+  const rl_history_resize_info info = p->info;
+  eng_relog_abort(c, p);
+  p->info = info;
+  return RL_OK;
+}
+
+int eng_resize_history(Engine* c, uint64_t history_entries, rl_history_resize_info* info) {
+  RelogPlan p;
+  if (const int rc = eng_relog_place(c, history_entries, &p)) return rc;
+  if (const int rc = eng_relog_commit(c, &p)) return rc;
+  if (info) *info = p.info;
+  return RL_OK;
+}
+
+// ---------------------------------------------------------------------------
+// rl_resize_arena on one engine: a new pair of arenas (the live one and the
+// sweep's compaction target), the used bytes copied device to device. Offsets
+// are kept, so no slot changes; the cursor (counters[4]) stays.
+// ---------------------------------------------------------------------------
+void eng_arena_abort(Engine* c, ArenaPlan* p) {
+  if (!p) return;
+  if (c && (p->arena || p->arena2)) (void)hipSetDevice(c->cfg.device);
+  if (p->arena) (void)hipFree(p->arena);
+  if (p->arena2) (void)hipFree(p->arena2);
+  *p = ArenaPlan{};
+}
+
+int eng_arena_check(Engine* c, uint64_t arena_bytes) {
+  if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
+  if (!arena_bytes || (arena_bytes & 15u) || arena_bytes / 16 > (1ull << 32))
+    return set_err(c, RL_E_INVALID, "gpu: rl_resize_arena: arena_bytes must be a multiple of 16 in [16, 2^36]");
+  return RL_OK;
+}
+
+int eng_arena_place(Engine* c, uint64_t arena_bytes, ArenaPlan* p) {
+  if (!p) return set_err(c, RL_E_INVALID, "gpu: null argument");
+  *p = ArenaPlan{};
+  if (const int rc = eng_arena_check(c, arena_bytes)) return rc;
+  RQ_SETTLE(c);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipStream_t st = c->stream;
+  HIPCHK(c, after_batches(c, st));
+  unsigned long long used16 = 0;
+  HIPCHK(c, hipMemcpyAsync(&used16, c->s[0].counters + 4, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (used16 > arena_bytes / 16)
+    return set_err(c, RL_E_ARENA_FULL, "gpu: rl_resize_arena: " + std::to_string(used16 * 16) +
+                                           " bytes are in use (rl_sweep compacts the arena)");
+  hipError_t e = dalloc(&p->arena, arena_bytes);
+  if (e == hipSuccess) e = dalloc(&p->arena2, arena_bytes);
+  if (e == hipSuccess && used16) e = hipMemcpyAsync(p->arena, c->arena, used16 * 16, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    eng_arena_abort(c, p);
+    return set_err(c, RL_E_HIP, std::string("gpu: rl_resize_arena: ") + hipGetErrorString(e) +
+                                    " (the old and the new pair of arenas coexist during the call)");
+  }
+  p->cap16 = arena_bytes / 16;
+  return RL_OK;
+}
+
+void eng_arena_commit(Engine* c, ArenaPlan* p) {
+  std::swap(c->arena, p->arena);  // (the plan now holds the old pair: freed below)
+  std::swap(c->arena2, p->arena2);
+  c->arena_cap16 = p->cap16;
+  c->cfg.arena_bytes = p->cap16 * 16;
+  eng_arena_abort(c, p);
+}
+
+int eng_resize_arena(Engine* c, uint64_t arena_bytes) {
+  ArenaPlan p;
+  if (const int rc = eng_arena_place(c, arena_bytes, &p)) return rc;
+  eng_arena_commit(c, &p);
   return RL_OK;
 }
 

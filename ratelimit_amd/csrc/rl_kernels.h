@@ -417,6 +417,21 @@ void launch_resize_place(const TableDev& t, const HashKey& hk, uint64_t nslots, 
 // their `slot` word; ctr[5] += entries stored. (t: still the OLD table.)
 void launch_resize_relink(const TableDev& t, uint64_t nslots, const uint32_t* map, unsigned long long* ctr,
                           hipStream_t st);
+// ---- the history log at another size (rl_resize_history, rl_relog.hip) ----
+// Copy the entries on the chains of t's live slots (nslots slots) into `to`
+// (LOG_PARTS partitions of to_cap entries, a power of two), each key's copies
+// contiguous, oldest lowest; map[i] = the new chain head of live slot i with a
+// chain (LOG_LOST: its walk accepts no entry). ctr (RELOG_CTR_WORDS zeroed
+// words, laid out like Engine::log_ctr): word 0 of line p = the entries asked
+// of partition p; line LOG_PARTS: [0] chains, [1] entries kept, [2] chains that
+// end in LOG_LOST, [3] the longest chain, [4] waves whose entries did not fit
+// (they wrote nothing). Only `to`, map and ctr are written.
+constexpr uint32_t RELOG_CTR_STATS = LOG_PARTS * LOG_CTR_STRIDE;
+constexpr uint32_t RELOG_CTR_WORDS = (LOG_PARTS + 1) * LOG_CTR_STRIDE;
+void launch_relog_place(const TableDev& t, uint64_t nslots, LogEnt* to, uint32_t to_cap, uint32_t* map,
+                        unsigned long long* ctr, hipStream_t st);
+// ring = map[i] for the live slots with a chain.
+void launch_relog_commit(Slot* slots, uint64_t nslots, const uint32_t* map, hipStream_t st);
 // ---- export / import of window records (rl_export_range, rl_import) ----
 // Device staging of one export call: the rl_records arrays (off: the records'
 // stem offsets; the host appends the total).

@@ -28,6 +28,7 @@
 #include <stdint.h>
 #include <cstdlib>
 
+#include "rl_chain.h"
 #include "rl_device.h"
 #include "rl_kernels.h"
 #include "rl_slot_img.h"
@@ -5144,31 +5145,9 @@ __global__ __launch_bounds__(256) void k_finish(const unsigned long long* __rest
   }
 }
 
-// Walk the history chain of slot si (tag `tag`, chain head `head`, newest window
-// cur_ws): f(entry, hop index) for each entry the log still holds, newest
-// first (stops where one was overwritten, or when f says so). f may store to
-// the entry's `slot` word (the resize's re-link): its other words are read first.
-template <typename F>
-__device__ inline void chain_walk_ent(const TableDev& t, uint32_t si, uint32_t tag, uint32_t head, uint32_t cur_ws, F f) {
-  uint32_t ptr = head, tprev = cur_ws, saved = LOG_NONE, power = 1, lam = 0;
-  for (uint32_t hops = 0; ptr != LOG_NONE && hops < LOG_MAX_HOPS && ptr != saved; hops++) {  // (log_find's checks)
-    const uint32_t pos = ptr & LOG_POS_MASK;
-    if (pos >= t.log_cap) return;
-    if (++lam == power) {
-      saved = ptr;
-      power <<= 1;
-      lam = 0;
-    }
-    LogEnt& e = t.log[(size_t)(ptr >> LOG_POS_BITS) * t.log_cap + pos];
-    if (e.slot != si || e.tag != tag || e.t_app > tprev) return;
-    const uint32_t t_app = e.t_app, prev = e.prev;
-    if (!f(e, hops)) return;
-    tprev = t_app;
-    ptr = prev;
-  }
-}
-
-// ... of slot s, f(entry record, hop index).
+// (chain_walk_ent, the walk of a slot's history chain entry by entry, lives in
+// rl_chain.h: rl_relog.hip compiles it too.)
+// The chain of slot s, f(entry record, hop index).
 template <typename F>
 __device__ inline void chain_walk(const TableDev& t, uint32_t si, const Slot& s, F f) {
   chain_walk_ent(t, si, s.tag, s.ring, s.cur.ws, [&](LogEnt& e, uint32_t hops) { return f(e.w, hops); });

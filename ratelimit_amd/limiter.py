@@ -655,6 +655,25 @@ class Backend:
         self.cfg.table_slots = table_slots
         return {f: getattr(info, f) for f, _ in abi.RlResizeInfo._fields_ if f != "reserved"}
 
+    def resize_history(self, history_entries: int) -> dict:
+        """rl_resize_history: every shard's history log is rebuilt at history_entries
+        (rounded as at creation; larger, smaller or equal: equal drops every entry no
+        live chain reaches), the live chains copied on the device, no answer
+        changed. Returns the rl_history_resize_info fields. Raises RedisError with
+        the call's status (RL_E_CAPACITY: the live chains do not fit) and leaves
+        the log as it was."""
+        info = abi.RlHistoryResizeInfo()
+        self._check(self.L.rl_resize_history(self.ctx, history_entries, C.byref(info)))
+        self.cfg.history_entries = info.entries_after // self.n_shards()
+        return {f: getattr(info, f) for f, _ in abi.RlHistoryResizeInfo._fields_ if f != "reserved"}
+
+    def resize_arena(self, arena_bytes: int) -> None:
+        """rl_resize_arena: every shard's long-stem arena (and the sweep's spare one)
+        becomes arena_bytes, the used bytes copied on the device. Raises RedisError
+        (RL_E_ARENA_FULL: more bytes are in use; sweep first) and changes nothing."""
+        self._check(self.L.rl_resize_arena(self.ctx, arena_bytes))
+        self.cfg.arena_bytes = arena_bytes
+
     # ---- export / import of live counters (resize, reshard, re-key)
     def n_shards(self) -> int:
         return max(int(self.cfg.n_shards), 1)
