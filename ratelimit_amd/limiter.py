@@ -994,8 +994,14 @@ def migrate(src: Backend, dst: Backend, chunk_slots: int = 1 << 20) -> dict:
     """Move every live counter of src into dst (any table_slots, history_entries,
     hash_seed or shard count): export_records -> import_records. Returns the
     summed rl_export_info (records, stem_bytes, keys, chains_lost; shard_slots
-    summed over shards; time_floor the source's). Raises RedisError when dst
-    cannot take a record (RL_E_TABLE_FULL / RL_E_ARENA_FULL: its status)."""
+    summed over shards; time_floor the source's). rl_import leaves dst's sweep
+    floor alone, so the source's floor is carried over with a sweep of dst at
+    that clock once every record is in: a request that src would refuse for its
+    clock (RL_E_TIME: the keys it swept may have held that window) is refused by
+    dst too, never counted afresh. The sweep evicts nothing src kept (src swept
+    at that floor itself) and leaves a higher floor of dst's own as it is.
+    Raises RedisError when dst cannot take a record (RL_E_TABLE_FULL /
+    RL_E_ARENA_FULL: its status)."""
     total = {"shard_slots": 0, "records": 0, "stem_bytes": 0, "keys": 0, "chains_lost": 0, "time_floor": 0}
     shards = set()
     for rec in src.export_records(chunk_slots):
@@ -1007,6 +1013,8 @@ def migrate(src: Backend, dst: Backend, chunk_slots: int = 1 << 20) -> dict:
             shards.add(rec["shard"])
             total["shard_slots"] += info["shard_slots"]
         dst.import_records(rec)
+    if total["time_floor"] > 0:
+        dst.sweep(total["time_floor"])
     return total
 
 
