@@ -40,6 +40,7 @@
 #include "rl_device.h"
 #include "rl_engine.h"
 #include "rl_kernels.h"
+#include "rl_shard_split.h"
 
 using namespace rl;
 
@@ -48,6 +49,8 @@ namespace {
 constexpr uint32_t MAX_LOCAL_SHARDS = 16;
 
 // One shard's worker: runs its router's collective steps on its own thread.
+// (A ctx of one shard has no thread; rl_resize and rl_resize_history still keep
+// its plan in w[0], placed on the caller's thread.)
 struct ShardWorker {
   enum Job { IDLE, BATCH, SYNC, RESIZE, FORGET, RELOG, EXIT };
   std::thread th;
@@ -85,7 +88,7 @@ struct rl_ctx {
   Engine* e[MAX_LOCAL_SHARDS] = {};
   CommRouter* comm = nullptr;  // rl_comm_init: multi-process routing (single-shard ctx)
   std::string last_error;
-  // shards of this ctx (n > 1)
+  // shards of this ctx (n > 1; w[0] also holds a one-shard ctx's resize plans)
   CommRouter* r[MAX_LOCAL_SHARDS] = {};
   ShardWorker w[MAX_LOCAL_SHARDS];
   std::mutex done_mu;
@@ -121,6 +124,40 @@ int from_engine(rl_ctx* c, Engine* e, int rc) {
   } while (0)
 
 uint32_t owner_of_host(uint64_t h, uint32_t n) { return (uint32_t)(((uint64_t)(uint32_t)h * n) >> 32); }
+
+// The sink rule: a maintenance call's own refusal goes where rl_last_error
+// reads it, a one-shard ctx's engine or the ctx. (rl_restore, rl_import,
+// rl_lookup, rl_export_range and older calls use plain fail: DESIGN.md §11.)
+int fail_call(rl_ctx* c, int code, const std::string& msg) {
+  return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg);
+}
+
+// A call's stem list split by owning shard. False: an entry's offsets decrease.
+bool split_by_owner(rl_ctx* c, uint32_t n, const uint8_t* stem_bytes, const uint32_t* stem_off,
+                    std::vector<rlsplit::Sub>* out) {
+  const HashKey& hk = c->e[0]->hk;
+  const uint32_t N = c->n;
+  auto owner = [&](const uint8_t* s, uint32_t len) { return owner_of_host(hash_stem_host(hk, s, len), N); };
+  return rlsplit::split(n, stem_bytes, stem_off, N, owner, out);
+}
+
+// The three resizes share one shape: these refusals and the size's check on
+// shard 0; the shards settle; every shard places its new memory beside the old
+// (table and log on the shards' workers, or here for a one-shard ctx; the arena
+// inline: small); all commit or all abort.
+int resize_refused(rl_ctx* c, const char* name) {
+  if (!c) return fail_call(c, RL_E_INVALID, "gpu: null ctx");
+  if (c->comm) return fail_call(c, RL_E_INVALID, std::string("gpu: ") + name + " is not for a ctx that joined a communicator");
+  return RL_OK;
+}
+
+// rc: the placements'. plan(j): shard j's plan; commit(engine, plan) -> rl_status (and takes the plan's info).
+template <typename PlanOf, typename Commit>
+int resize_commit_all(rl_ctx* c, int rc, PlanOf plan, Commit commit) {
+  for (uint32_t j = 0; j < c->n && !rc; j++) rc = from_engine(c, c->e[j], commit(c->e[j], plan(j)));
+  for (uint32_t j = 0; j < c->n; j++) eng_plan_abort(c->e[j], plan(j));  // (what was not committed)
+  return rc;
+}
 
 void worker_main(rl_ctx* c, uint32_t j) {
   (void)hipSetDevice(c->cfg.shard_device[j]);
@@ -650,34 +687,16 @@ int rl_restore(rl_ctx* c, const rl_restore_batch* r) {
   if (const int src = settle(c)) return src;
   if (c->n == 1) return eng_restore(c->e[0], r);
   // route the SET records by owner on the host (restores are rare)
-  const uint32_t N = c->n;
-  std::vector<std::vector<uint32_t>> idx(N);
-  for (uint32_t i = 0; i < r->n; i++) {
-    const uint32_t a = r->stem_off[i], b = r->stem_off[i + 1];
-    if (b < a) return fail(c, RL_E_INVALID, "gpu: restore stem offsets");
-    idx[owner_of_host(hash_stem_host(c->e[0]->hk, r->stem_bytes + a, b - a), N)].push_back(i);
-  }
-  for (uint32_t j = 0; j < N; j++) {
-    if (idx[j].empty()) continue;
-    std::vector<uint8_t> stems, unit, lc;
-    std::vector<uint32_t> off{0}, count;
-    std::vector<int64_t> now;
-    for (uint32_t i : idx[j]) {
-      stems.insert(stems.end(), r->stem_bytes + r->stem_off[i], r->stem_bytes + r->stem_off[i + 1]);
-      off.push_back((uint32_t)stems.size());
-      unit.push_back(r->unit[i]);
-      now.push_back(r->now[i]);
-      count.push_back(r->count[i]);
-      lc.push_back(r->lc ? r->lc[i] : 0);
-    }
-    rl_restore_batch sub{};
-    sub.n = (uint32_t)idx[j].size();
-    sub.stem_bytes = stems.data();
-    sub.stem_off = off.data();
-    sub.unit = unit.data();
-    sub.now = now.data();
-    sub.count = count.data();
-    sub.lc = lc.data();
+  std::vector<rlsplit::Sub> part;
+  if (!split_by_owner(c, r->n, r->stem_bytes, r->stem_off, &part)) return fail(c, RL_E_INVALID, "gpu: restore stem offsets");
+  for (uint32_t j = 0; j < c->n; j++) {
+    const rlsplit::Sub& s = part[j];
+    if (s.idx.empty()) continue;
+    const auto unit = rlsplit::take(r->unit, s.idx), lc = rlsplit::take(r->lc, s.idx);
+    const auto now = rlsplit::take(r->now, s.idx);
+    const auto count = rlsplit::take(r->count, s.idx);
+    const rl_restore_batch sub{(uint32_t)s.idx.size(), 0,          s.stems.data(), s.off.data(),
+                               unit.data(),            now.data(), count.data(),   lc.data()};
     const int rc = from_engine(c, c->e[j], eng_restore(c->e[j], &sub));
     if (rc) return rc;
   }
@@ -790,33 +809,26 @@ int rl_export_range(rl_ctx* c, uint32_t shard, uint64_t slot_begin, uint64_t slo
 }
 
 int rl_resize(rl_ctx* c, uint64_t table_slots, rl_resize_info* info) {
-  // (a single-shard ctx reports through its engine: rl_last_error reads it there)
-  auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };
-  if (!c) return bad(RL_E_INVALID, "gpu: null ctx");
-  if (c->comm) return bad(RL_E_INVALID, "gpu: rl_resize is not for a ctx that joined a communicator");
+  if (const int rc = resize_refused(c, "rl_resize")) return rc;
   if (const int rc = from_engine(c, c->e[0], eng_resize_check(c->e[0], table_slots))) return rc;
-  if (c->n == 1) {
-    const int rc = eng_resize(c->e[0], table_slots, info);
-    if (!rc) c->cfg.table_slots = table_slots;
-    return rc;
-  }
   if (const int src = settle_local(c)) return src;
-  // every shard places its keys in a new table on its own device and worker;
-  // nothing of any shard has changed until all of them have succeeded
   for (uint32_t j = 0; j < c->n; j++) c->w[j].rs_slots = table_slots;
-  int rc = run_shards(c, ShardWorker::RESIZE);
   rl_resize_info sum{};
-  for (uint32_t j = 0; j < c->n && !rc; j++) {
-    rc = from_engine(c, c->e[j], eng_resize_commit(c->e[j], &c->w[j].rs_plan));
-    const rl_resize_info& x = c->w[j].rs_plan.info;
-    sum.slots_before += x.slots_before;
-    sum.slots_after += x.slots_after;
-    sum.keys += x.keys;
-    sum.tombstones_dropped += x.tombstones_dropped;
-    sum.log_entries_relinked += x.log_entries_relinked;
-    sum.longest_probe = std::max(sum.longest_probe, x.longest_probe);
-  }
-  for (uint32_t j = 0; j < c->n; j++) eng_resize_abort(c->e[j], &c->w[j].rs_plan);  // (what was not committed)
+  const int placed = c->n == 1 ? eng_resize_place(c->e[0], table_slots, &c->w[0].rs_plan)  // (no workers: here)
+                               : run_shards(c, ShardWorker::RESIZE);
+  const int rc = resize_commit_all(
+      c, placed, [&](uint32_t j) { return &c->w[j].rs_plan; },
+      [&](Engine* e, ResizePlan* p) {
+        const int rc = eng_resize_commit(e, p);
+        const rl_resize_info& x = p->info;
+        sum.slots_before += x.slots_before;
+        sum.slots_after += x.slots_after;
+        sum.keys += x.keys;
+        sum.tombstones_dropped += x.tombstones_dropped;
+        sum.log_entries_relinked += x.log_entries_relinked;
+        sum.longest_probe = std::max(sum.longest_probe, x.longest_probe);
+        return rc;
+      });
   if (rc) return rc;
   c->cfg.table_slots = table_slots;
   if (info) *info = sum;
@@ -824,36 +836,29 @@ int rl_resize(rl_ctx* c, uint64_t table_slots, rl_resize_info* info) {
 }
 
 int rl_resize_history(rl_ctx* c, uint64_t history_entries, rl_history_resize_info* info) {
-  // (a single-shard ctx reports through its engine: rl_last_error reads it there)
-  auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };
-  if (!c) return bad(RL_E_INVALID, "gpu: null ctx");
-  if (c->comm) return bad(RL_E_INVALID, "gpu: rl_resize_history is not for a ctx that joined a communicator");
+  if (const int rc = resize_refused(c, "rl_resize_history")) return rc;
   if (const int rc = from_engine(c, c->e[0], eng_relog_check(c->e[0], history_entries))) return rc;
-  if (c->n == 1) {
-    const int rc = eng_resize_history(c->e[0], history_entries, info);
-    if (!rc) c->cfg.history_entries = c->e[0]->cfg.history_entries;
-    return rc;
-  }
   if (const int src = settle_local(c)) return src;
-  // every shard copies its live chains into a new log on its own device and
-  // worker; nothing of any shard has changed until all of them have succeeded
   for (uint32_t j = 0; j < c->n; j++) c->w[j].rl_entries = history_entries;
-  int rc = run_shards(c, ShardWorker::RELOG);
   rl_history_resize_info sum{};
-  for (uint32_t j = 0; j < c->n && !rc; j++) {
-    rc = from_engine(c, c->e[j], eng_relog_commit(c->e[j], &c->w[j].rl_plan));
-    const rl_history_resize_info& x = c->w[j].rl_plan.info;
-    sum.entries_before += x.entries_before;
-    sum.entries_after += x.entries_after;
-    sum.written_before += x.written_before;
-    sum.entries_kept += x.entries_kept;
-    sum.entries_dropped += x.entries_dropped;
-    sum.chains += x.chains;
-    sum.chains_lost += x.chains_lost;
-    sum.fill_max = std::max(sum.fill_max, x.fill_max);
-    sum.longest_chain = std::max(sum.longest_chain, x.longest_chain);
-  }
-  for (uint32_t j = 0; j < c->n; j++) eng_relog_abort(c->e[j], &c->w[j].rl_plan);  // (what was not committed)
+  const int placed = c->n == 1 ? eng_relog_place(c->e[0], history_entries, &c->w[0].rl_plan)  // (no workers: here)
+                               : run_shards(c, ShardWorker::RELOG);
+  const int rc = resize_commit_all(
+      c, placed, [&](uint32_t j) { return &c->w[j].rl_plan; },
+      [&](Engine* e, RelogPlan* p) {
+        const int rc = eng_relog_commit(e, p);
+        const rl_history_resize_info& x = p->info;
+        sum.entries_before += x.entries_before;
+        sum.entries_after += x.entries_after;
+        sum.written_before += x.written_before;
+        sum.entries_kept += x.entries_kept;
+        sum.entries_dropped += x.entries_dropped;
+        sum.chains += x.chains;
+        sum.chains_lost += x.chains_lost;
+        sum.fill_max = std::max(sum.fill_max, x.fill_max);
+        sum.longest_chain = std::max(sum.longest_chain, x.longest_chain);
+        return rc;
+      });
   if (rc) return rc;
   c->cfg.history_entries = c->e[0]->cfg.history_entries;
   if (info) *info = sum;
@@ -861,25 +866,18 @@ int rl_resize_history(rl_ctx* c, uint64_t history_entries, rl_history_resize_inf
 }
 
 int rl_resize_arena(rl_ctx* c, uint64_t arena_bytes) {
-  auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };
-  if (!c) return bad(RL_E_INVALID, "gpu: null ctx");
-  if (c->comm) return bad(RL_E_INVALID, "gpu: rl_resize_arena is not for a ctx that joined a communicator");
+  if (const int rc = resize_refused(c, "rl_resize_arena")) return rc;
   if (const int rc = from_engine(c, c->e[0], eng_arena_check(c->e[0], arena_bytes))) return rc;
-  if (c->n == 1) {
-    const int rc = eng_resize_arena(c->e[0], arena_bytes);
-    if (!rc) c->cfg.arena_bytes = arena_bytes;
-    return rc;
-  }
   if (const int src = settle_local(c)) return src;
-  // every shard gets its new pair and copy first (small: no worker job); no
-  // shard swaps unless all of them have
   ArenaPlan plan[MAX_LOCAL_SHARDS];
   int rc = RL_OK;
   for (uint32_t j = 0; j < c->n && !rc; j++) rc = from_engine(c, c->e[j], eng_arena_place(c->e[j], arena_bytes, &plan[j]));
-  for (uint32_t j = 0; j < c->n; j++) {
-    if (!rc) eng_arena_commit(c->e[j], &plan[j]);
-    else eng_arena_abort(c->e[j], &plan[j]);
-  }
+  rc = resize_commit_all(
+      c, rc, [&](uint32_t j) { return &plan[j]; },
+      [](Engine* e, ArenaPlan* p) {
+        eng_arena_commit(e, p);
+        return (int)RL_OK;
+      });
   if (rc) return rc;
   c->cfg.arena_bytes = arena_bytes;
   return RL_OK;
@@ -893,36 +891,16 @@ int rl_import(rl_ctx* c, const rl_records* in) {
   // the whole call is checked first (a bad record leaves every shard untouched),
   // then the records go to their owners, routed on the host like rl_restore's
   if (const int rc = from_engine(c, c->e[0], eng_import_check(c->e[0], in))) return rc;
-  const uint32_t N = c->n;
-  std::vector<std::vector<uint32_t>> idx(N);
-  for (uint32_t i = 0; i < in->n; i++) {
-    const uint32_t a = in->stem_off[i], b = in->stem_off[i + 1];
-    idx[owner_of_host(hash_stem_host(c->e[0]->hk, in->stem_bytes + a, b - a), N)].push_back(i);
-  }
-  for (uint32_t j = 0; j < N; j++) {
-    if (idx[j].empty()) continue;
-    std::vector<uint8_t> stems, unit, flags;
-    std::vector<uint32_t> off{0}, ws, count, expire, lc;
-    for (uint32_t i : idx[j]) {
-      stems.insert(stems.end(), in->stem_bytes + in->stem_off[i], in->stem_bytes + in->stem_off[i + 1]);
-      off.push_back((uint32_t)stems.size());
-      unit.push_back(in->unit[i]);
-      flags.push_back(in->flags ? in->flags[i] : 0);
-      ws.push_back(in->ws[i]);
-      count.push_back(in->count[i]);
-      expire.push_back(in->expire[i]);
-      lc.push_back(in->lc[i]);
-    }
-    rl_records sub{};
-    sub.n = (uint32_t)idx[j].size();
-    sub.stem_bytes = stems.data();
-    sub.stem_off = off.data();
-    sub.unit = unit.data();
-    sub.flags = flags.data();
-    sub.ws = ws.data();
-    sub.count = count.data();
-    sub.expire = expire.data();
-    sub.lc = lc.data();
+  std::vector<rlsplit::Sub> part;
+  split_by_owner(c, in->n, in->stem_bytes, in->stem_off, &part);
+  for (uint32_t j = 0; j < c->n; j++) {
+    rlsplit::Sub& s = part[j];
+    if (s.idx.empty()) continue;
+    auto unit = rlsplit::take(in->unit, s.idx), flags = rlsplit::take(in->flags, s.idx);
+    auto ws = rlsplit::take(in->ws, s.idx), count = rlsplit::take(in->count, s.idx);
+    auto expire = rlsplit::take(in->expire, s.idx), lc = rlsplit::take(in->lc, s.idx);
+    const rl_records sub{(uint32_t)s.idx.size(), 0,         0,            s.stems.data(), s.off.data(), unit.data(),
+                         flags.data(),           ws.data(), count.data(), expire.data(),  lc.data()};
     const int rc = from_engine(c, c->e[j], eng_import(c->e[j], &sub));
     if (rc) return rc;
   }
@@ -938,60 +916,36 @@ int rl_lookup(rl_ctx* c, const rl_keys* in, rl_key_state* out) {
   // go to their owners, routed on the host like rl_import's records, and the
   // answers come back in the caller's order
   if (const int rc = from_engine(c, c->e[0], eng_lookup_check(c->e[0], in, out))) return rc;
-  const uint32_t N = c->n;
-  std::vector<std::vector<uint32_t>> idx(N);
-  for (uint32_t i = 0; i < in->n; i++) {
-    const uint32_t a = in->stem_off[i], b = in->stem_off[i + 1];
-    idx[owner_of_host(hash_stem_host(c->e[0]->hk, in->stem_bytes + a, b - a), N)].push_back(i);
-  }
-  struct Sub {
-    std::vector<uint8_t> stems, unit, status, found;
-    std::vector<uint32_t> off{0}, count, expire, lc;
-    std::vector<int64_t> now;
-  };
-  std::vector<Sub> sub(N);
-  for (uint32_t j = 0; j < N; j++) {
-    if (idx[j].empty()) continue;
-    Sub& s = sub[j];
-    for (uint32_t i : idx[j]) {
-      s.stems.insert(s.stems.end(), in->stem_bytes + in->stem_off[i], in->stem_bytes + in->stem_off[i + 1]);
-      s.off.push_back((uint32_t)s.stems.size());
-      s.unit.push_back(in->unit[i]);
-      s.now.push_back(in->now[i]);
-    }
-    const size_t m = idx[j].size();
+  std::vector<rlsplit::Sub> part;
+  split_by_owner(c, in->n, in->stem_bytes, in->stem_off, &part);
+  // (the shards' answers lie one after the other in arrays of the call's size)
+  std::vector<uint8_t> status(in->n), found(in->n);
+  std::vector<uint32_t> count(in->n), expire(in->n), lc(in->n);
+  size_t at = 0;
+  for (uint32_t j = 0; j < c->n; at += part[j++].idx.size()) {
+    rlsplit::Sub& s = part[j];
+    if (s.idx.empty()) continue;
+    const auto unit = rlsplit::take(in->unit, s.idx);
+    const auto now = rlsplit::take(in->now, s.idx);
     s.stems.push_back(0);  // (never null, even when every stem is empty)
-    s.status.resize(m);
-    s.found.resize(m);
-    s.count.resize(m);
-    s.expire.resize(m);
-    s.lc.resize(m);
-    rl_keys k{};
-    k.n = (uint32_t)m;
-    k.stem_bytes = s.stems.data();
-    k.stem_off = s.off.data();
-    k.unit = s.unit.data();
-    k.now = s.now.data();
-    rl_key_state o{s.status.data(), s.found.data(), s.count.data(), s.expire.data(), s.lc.data()};
+    const rl_keys k{(uint32_t)s.idx.size(), 0, s.stems.data(), s.off.data(), unit.data(), now.data()};
+    rl_key_state o{status.data() + at, found.data() + at, count.data() + at, expire.data() + at, lc.data() + at};
     if (const int rc = from_engine(c, c->e[j], eng_lookup(c->e[j], &k, &o))) return rc;  // (nothing scattered yet)
   }
-  for (uint32_t j = 0; j < N; j++)
-    for (size_t x = 0; x < idx[j].size(); x++) {
-      const uint32_t i = idx[j][x];
-      out->status[i] = sub[j].status[x];
-      out->found[i] = sub[j].found[x];
-      out->count[i] = sub[j].count[x];
-      out->expire[i] = sub[j].expire[x];
-      out->lc[i] = sub[j].lc[x];
-    }
+  at = 0;
+  for (uint32_t j = 0; j < c->n; at += part[j++].idx.size()) {
+    rlsplit::put(out->status, part[j].idx, status.data() + at);
+    rlsplit::put(out->found, part[j].idx, found.data() + at);
+    rlsplit::put(out->count, part[j].idx, count.data() + at);
+    rlsplit::put(out->expire, part[j].idx, expire.data() + at);
+    rlsplit::put(out->lc, part[j].idx, lc.data() + at);
+  }
   return RL_OK;
 }
 
 int rl_forget(rl_ctx* c, const rl_stems* in, uint32_t* removed, rl_forget_info* info) {
-  // (a single-shard ctx reports through its engine: rl_last_error reads it there)
-  auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };
-  if (!c || !in) return bad(RL_E_INVALID, "gpu: null argument");
-  if (c->comm) return bad(RL_E_INVALID, "gpu: rl_forget is not for a ctx that joined a communicator");
+  if (!c || !in) return fail_call(c, RL_E_INVALID, "gpu: null argument");
+  if (c->comm) return fail_call(c, RL_E_INVALID, "gpu: rl_forget is not for a ctx that joined a communicator");
   if (c->n == 1) return eng_forget(c->e[0], in, removed, info);
   // the whole call is checked first: a bad call changes no shard
   if (const int rc = from_engine(c, c->e[0], eng_forget_check(c->e[0], in))) return rc;
@@ -1023,49 +977,34 @@ int rl_forget(rl_ctx* c, const rl_stems* in, uint32_t* removed, rl_forget_info* 
   }
   // keyed stems go to their owners, routed on the host like rl_lookup's keys,
   // and the counts come back in the caller's order
-  std::vector<std::vector<uint32_t>> idx(N);
-  for (uint32_t i = 0; i < in->n; i++) {
-    const uint32_t a = in->stem_off[i], b = in->stem_off[i + 1];
-    idx[owner_of_host(hash_stem_host(c->e[0]->hk, in->stem_bytes + a, b - a), N)].push_back(i);
-  }
+  std::vector<rlsplit::Sub> part;
+  split_by_owner(c, in->n, in->stem_bytes, in->stem_off, &part);
   std::vector<std::vector<uint32_t>> got(N);
   for (uint32_t j = 0; j < N; j++) {
-    if (idx[j].empty()) continue;
-    std::vector<uint8_t> stems;
-    std::vector<uint32_t> off{0};
-    for (uint32_t i : idx[j]) {
-      stems.insert(stems.end(), in->stem_bytes + in->stem_off[i], in->stem_bytes + in->stem_off[i + 1]);
-      off.push_back((uint32_t)stems.size());
-    }
-    got[j].resize(idx[j].size());
-    rl_stems sub{};
-    sub.n = (uint32_t)idx[j].size();
-    sub.flags = in->flags;
-    sub.stem_bytes = stems.data();
-    sub.stem_off = off.data();
+    const rlsplit::Sub& s = part[j];
+    if (s.idx.empty()) continue;
+    got[j].resize(s.idx.size());
+    const rl_stems sub{(uint32_t)s.idx.size(), in->flags, s.stems.data(), s.off.data()};
     rl_forget_info x{};
     if (const int rc = from_engine(c, c->e[j], eng_forget(c->e[j], &sub, got[j].data(), &x))) return rc;
     add(x);
   }
   if (removed)
-    for (uint32_t j = 0; j < N; j++)
-      for (size_t x = 0; x < idx[j].size(); x++) removed[idx[j][x]] = got[j][x];
+    for (uint32_t j = 0; j < N; j++) rlsplit::put(removed, part[j].idx, got[j].data());
   if (info) *info = sum;
   return RL_OK;
 }
 
 int rl_scan(rl_ctx* c, const rl_scan_query* q, rl_scan_cursor* cur, rl_records* out, rl_scan_prefix_sum* by_prefix,
             rl_scan_info* info) {
-  // (a single-shard ctx reports through its engine: rl_last_error reads it there)
-  auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };
-  if (!c || !q || !cur) return bad(RL_E_INVALID, "gpu: null argument");
-  if (c->comm) return bad(RL_E_INVALID, "gpu: rl_scan is not for a ctx that joined a communicator");
-  if (cur->reserved) return bad(RL_E_INVALID, "gpu: rl_scan: cursor's reserved field not zero");
-  if (cur->shard > c->n) return bad(RL_E_INVALID, "gpu: rl_scan: cursor shard beyond n_shards");
+  if (!c || !q || !cur) return fail_call(c, RL_E_INVALID, "gpu: null argument");
+  if (c->comm) return fail_call(c, RL_E_INVALID, "gpu: rl_scan is not for a ctx that joined a communicator");
+  if (cur->reserved) return fail_call(c, RL_E_INVALID, "gpu: rl_scan: cursor's reserved field not zero");
+  if (cur->shard > c->n) return fail_call(c, RL_E_INVALID, "gpu: rl_scan: cursor shard beyond n_shards");
   // the whole call is checked first: a failed call writes nothing
   if (const int rc = from_engine(c, c->e[0], eng_scan_check(c->e[0], q, out))) return rc;
   if (cur->shard == c->n) {  // the scan is complete: the empty answer
-    if (cur->slot) return bad(RL_E_INVALID, "gpu: rl_scan: a finished cursor's slot is 0");
+    if (cur->slot) return fail_call(c, RL_E_INVALID, "gpu: rl_scan: a finished cursor's slot is 0");
     if (out) {
       out->n = 0;
       out->stem_off[0] = 0;
@@ -1089,14 +1028,11 @@ int rl_scan(rl_ctx* c, const rl_scan_query* q, rl_scan_cursor* cur, rl_records* 
 }
 
 int rl_hot_keys(rl_ctx* c, const rl_hot_query* q, rl_records* out, rl_hot_info* info) {
-  // (a single-shard ctx reports through its engine: rl_last_error reads it there)
-  auto bad = [&](int code, const char* msg) { return c && c->n == 1 ? eng_fail(c->e[0], code, msg) : fail(c, code, msg); };
-  if (!c || !q || !info) return bad(RL_E_INVALID, "gpu: null argument");
-  if (c->comm) return bad(RL_E_INVALID, "gpu: rl_hot_keys is not for a ctx that joined a communicator");
+  if (!c || !q || !info) return fail_call(c, RL_E_INVALID, "gpu: null argument");
+  if (c->comm) return fail_call(c, RL_E_INVALID, "gpu: rl_hot_keys is not for a ctx that joined a communicator");
   // the whole call is checked first: a failed call writes nothing
-  if (q->k && (!out || !out->stem_off || !out->unit || !out->flags || !out->ws || !out->count || !out->expire ||
-               !out->lc || (out->stem_cap && !out->stem_bytes)))
-    return bad(RL_E_INVALID, "gpu: rl_hot_keys: null rl_records (or one of its arrays) with k > 0");
+  if (q->k && (!out || !records_check(out, true)))
+    return fail_call(c, RL_E_INVALID, "gpu: rl_hot_keys: null rl_records (or one of its arrays) with k > 0");
   for (uint32_t j = 0; j < c->n; j++)
     if (const int rc = from_engine(c, c->e[j], eng_hot_check(c->e[j], q))) return rc;
   if (const int src = settle_local(c)) return src;
@@ -1123,9 +1059,8 @@ int rl_hot_keys(rl_ctx* c, const rl_hot_query* q, rl_records* out, rl_hot_info* 
   *info = sum;
   if (!out) return RL_OK;
   if (top.size() > out->n || nb > out->stem_cap || nb > 0xFFFFFFFFull)
-    return bad(RL_E_CAPACITY, ("gpu: rl_hot_keys: the answer holds " + std::to_string(top.size()) + " records / " +
-                               std::to_string(nb) + " stem bytes: larger than rl_records")
-                                  .c_str());
+    return fail_call(c, RL_E_CAPACITY, "gpu: rl_hot_keys: the answer holds " + std::to_string(top.size()) + " records / " +
+                                           std::to_string(nb) + " stem bytes: larger than rl_records");
   out->n = (uint32_t)top.size();
   if (out->stem_off) out->stem_off[0] = 0;
   uint32_t at = 0;

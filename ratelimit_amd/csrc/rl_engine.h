@@ -7,12 +7,15 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/ratelimit_hip.h"
 #include "rl_device.h"
 #include "rl_kernels.h"
 #include "rl_match.h"
+
+#define RL_INTERNAL __attribute__((visibility("hidden")))  // not part of the library's symbol list
 
 namespace rl {
 
@@ -359,6 +362,9 @@ int eng_lookup(Engine* c, const rl_keys* in, rl_key_state* out);
 // q->k matching records in any order (record i's stem: stem[off[i]] .. + len[i])
 // and info's slots / matched / hits / time_floor; threshold and above are the
 // merge's (rl_api.hip). The call owns its device scratch and frees it.
+// records_check: the arrays an rl_records needs are there (every_column: also
+// for n == 0, as rl_hot_keys asks of its output).
+RL_INTERNAL bool records_check(const rl_records* r, bool every_column = false);
 struct HotAnswer {
   std::vector<uint8_t> stem, unit;
   std::vector<uint32_t> off, len, ws, count, expire, lc;
@@ -378,32 +384,53 @@ int eng_scan(Engine* c, const rl_scan_query* q, uint64_t* slot, rl_records* out,
 // scan. removed ([in->n]) and info may be null; *info is this engine's alone.
 int eng_forget_check(Engine* c, const rl_stems* in);
 int eng_forget(Engine* c, const rl_stems* in, uint32_t* removed, rl_forget_info* info);
-// rl_resize on this engine. One call (eng_resize), or in two steps for a ctx of
-// several shards: eng_resize_place puts every live key into a new table beside
-// the old one and changes nothing of the engine (any failure leaves the plan
-// empty); once every shard has placed, eng_resize_commit re-points the history
-// log, swaps the tables and frees the old one (p->info is then complete), else
-// eng_resize_abort frees what was placed. eng_resize_check: the size alone.
+// Device memory with one owner: a call's own scratch, freed when the call
+// returns, or what a resize plan has placed, until its commit hands it to the
+// engine (swap: the holder then owns, and frees, what the engine had).
+struct DevBufs {
+  std::vector<void*> p;
+  DevBufs& operator=(DevBufs&& o) {  // (o leaves with what this held, and frees it)
+    p.swap(o.p);
+    return *this;
+  }
+  ~DevBufs() {
+    for (void* q : p) (void)hipFree(q);
+  }
+  template <typename T>
+  hipError_t get(T** out, size_t count) {
+    const hipError_t e = hipMalloc((void**)out, (count ? count : 1) * sizeof(T));
+    if (e == hipSuccess) p.push_back(*out);
+    return e;
+  }
+  template <typename T>
+  void swap(T** engine, T** mine) {
+    for (void*& q : p)
+      if (q == *mine) q = *engine;
+    std::swap(*engine, *mine);
+  }
+};
+
+// rl_resize, rl_resize_history and rl_resize_arena on this engine, in two
+// steps, so that a ctx of several shards changes none of them unless all can
+// change: eng_*_place builds the new table / log / pair of
+// arenas beside the old one and changes nothing of the engine (whatever it
+// returns but RL_OK, the engine is as it was and the plan is empty); once
+// every shard has placed, eng_*_commit writes the one thing that changes in
+// place, swaps old for new and frees the old (p->info is then complete), else
+// eng_plan_abort frees what was placed. eng_*_check: the size alone.
 struct ResizePlan {
-  Slot* slots = nullptr;              // the new table (after the commit's swap: the old one)
+  DevBufs mem;
+  Slot* slots = nullptr;              // the new table
   uint32_t* map = nullptr;            // [old nslots] new index of each live old slot
   unsigned long long* ctr = nullptr;  // [RESIZE_CTR_WORDS]
   uint64_t nslots = 0;
   rl_resize_info info{};
 };
-int eng_resize_check(Engine* c, uint64_t table_slots);
-int eng_resize_place(Engine* c, uint64_t table_slots, ResizePlan* p);
-int eng_resize_commit(Engine* c, ResizePlan* p);
-void eng_resize_abort(Engine* c, ResizePlan* p);
-int eng_resize(Engine* c, uint64_t table_slots, rl_resize_info* info);
-// rl_resize_history on this engine, in rl_resize's two steps.
-// eng_relog_place copies the entries on live chains into a new log beside the
-// old one and changes nothing of the engine (any failure leaves the plan
-// empty); once every shard has placed, eng_relog_commit stores the new chain
-// heads, sets the append counters, swaps the logs and frees the old one, else
-// eng_relog_abort frees what was placed. eng_relog_check: the size alone.
+// (eng_relog_place copies the entries on live chains; eng_relog_commit stores
+// the new chain heads and sets the append counters)
 struct RelogPlan {
-  LogEnt* log = nullptr;              // the new log (after the commit's swap: the old one)
+  DevBufs mem;
+  LogEnt* log = nullptr;              // the new log
   uint32_t* map = nullptr;            // [nslots] new chain head of each live slot with a chain
   unsigned long long* ctr = nullptr;  // [RELOG_CTR_WORDS]
   uint32_t log_cap = 0;
@@ -411,22 +438,28 @@ struct RelogPlan {
   uint64_t appended = 0;                 // the old append counters' sum
   rl_history_resize_info info{};
 };
-int eng_relog_check(Engine* c, uint64_t history_entries);
-int eng_relog_place(Engine* c, uint64_t history_entries, RelogPlan* p);
-int eng_relog_commit(Engine* c, RelogPlan* p);
-void eng_relog_abort(Engine* c, RelogPlan* p);
-int eng_resize_history(Engine* c, uint64_t history_entries, rl_history_resize_info* info);
-// rl_resize_arena on this engine, likewise: eng_arena_place allocates the new
-// pair and copies the used bytes, eng_arena_commit swaps and frees the old pair.
+// (eng_arena_place copies the used bytes; nothing is written in place)
 struct ArenaPlan {
+  DevBufs mem;
   uint8_t *arena = nullptr, *arena2 = nullptr;
   uint64_t cap16 = 0;
 };
+// Free what a plan holds and leave it empty (an empty plan: nothing happens).
+template <typename Plan>
+void eng_plan_abort(Engine* c, Plan* p) {
+  if (!p) return;
+  if (c && !p->mem.p.empty()) (void)hipSetDevice(c->cfg.device);
+  *p = Plan{};
+}
+int eng_resize_check(Engine* c, uint64_t table_slots);
+int eng_resize_place(Engine* c, uint64_t table_slots, ResizePlan* p);
+int eng_resize_commit(Engine* c, ResizePlan* p);
+int eng_relog_check(Engine* c, uint64_t history_entries);
+int eng_relog_place(Engine* c, uint64_t history_entries, RelogPlan* p);
+int eng_relog_commit(Engine* c, RelogPlan* p);
 int eng_arena_check(Engine* c, uint64_t arena_bytes);
 int eng_arena_place(Engine* c, uint64_t arena_bytes, ArenaPlan* p);
 void eng_arena_commit(Engine* c, ArenaPlan* p);
-void eng_arena_abort(Engine* c, ArenaPlan* p);
-int eng_resize_arena(Engine* c, uint64_t arena_bytes);
 
 // Owner side of a routed batch, pipelined on the engine's streams like
 // eng_do_limit_async: unpack the n received wire records (chunks of n_src

@@ -1,7 +1,7 @@
-// rl_api.hip — the extern "C" boundary of libratelimit_hip.so
-// (include/ratelimit_hip.h). Owns the HBM table, two sets of per-batch scratch
-// and the HIP streams; every entry point maps the device error words to an
-// rl_status.
+// rl_engine.hip — one table shard on one GPU (rl_engine.h): the batch path,
+// the request path, snapshot, sweep and debug; the maintenance calls are
+// rl_maint.hip. Owns the HBM table, the sets of per-batch scratch and the HIP
+// streams; every entry point maps the device error words to an rl_status.
 //
 // Batches submitted with eng_do_limit_async(stream = NULL) are pipelined: batch
 // t's table-free stage A (validate, hash, sort, segment) runs on scratch buffer
@@ -28,16 +28,91 @@
 #include "rl_log_geom.h"
 #include "rl_match.h"
 #include "rl_engine.h"
+#include "rl_engine_int.h"
 
 using namespace rl;
 
+static thread_local std::string g_err;
 
+// The helpers rl_maint.hip shares (rl_engine_int.h).
+namespace rl {
+
+int set_err(Engine* c, int code, const std::string& msg) {
+  if (c) c->last_error = msg;
+  else g_err = msg;
+  return code;
+}
+
+int map_err(Engine* c, uint32_t e) {
+  if (!e) return RL_OK;
+  if (e & ERR_TIME) return set_err(c, RL_E_TIME, "gpu: now outside [0, 2^32-172800] or before the last sweep");
+  if (e & ERR_HISTORY)
+    return set_err(c, RL_E_TIME,
+                   "gpu: a request's window is older than its key's history holds (more than 8 windows and "
+                   "div + expiration_jitter_max_seconds behind the key's newest, or the history log overwrote it: "
+                   "raise history_entries)");
+  if (e & ERR_INVALID) return set_err(c, RL_E_INVALID, "gpu: malformed batch (unit, rule id, request index or stem offsets)");
+  if (e & ERR_TABLE_FULL) return set_err(c, RL_E_TABLE_FULL, "gpu: counter table full (raise table_slots or sweep)");
+  if (e & ERR_ARENA_FULL) return set_err(c, RL_E_ARENA_FULL, "gpu: long-stem arena full (raise arena_bytes)");
+  return set_err(c, RL_E_INTERNAL, "gpu: unknown device error");
+}
+
+// Order stream st after every batch submitted so far: each buffer's last
+// batch to its end (a batch's k_finish may still run after the next batch's
+// stage B has started: that waits for b_table only).
+hipError_t after_batches(Engine* c, hipStream_t st) {
+  for (uint32_t k = 0; k < NBUF; k++) {
+    const hipError_t e = hipStreamWaitEvent(st, c->b_done[k], 0);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// The history log's append counters (LOG_PARTS) and its lost-lookup count.
+hipError_t log_ctr_get(Engine* c, std::vector<unsigned long long>& ctr, unsigned long long* lost,
+                       unsigned long long* refused) {
+  std::vector<unsigned long long> h((size_t)(LOG_PARTS + 1) * LOG_CTR_STRIDE);
+  hipError_t e = hipMemcpyAsync(h.data(), c->log_ctr, h.size() * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return e;
+  ctr.resize(LOG_PARTS);
+  for (uint32_t k = 0; k < LOG_PARTS; k++) ctr[k] = h[(size_t)k * LOG_CTR_STRIDE];
+  if (lost) *lost = h[(size_t)LOG_PARTS * LOG_CTR_STRIDE];
+  if (refused) *refused = h[(size_t)LOG_PARTS * LOG_CTR_STRIDE + 1];
+  return hipSuccess;
+}
+
+TableDev table_view(Engine* c) {
+  TableDev t;
+  t.slots = c->slots;
+  t.log = c->log;
+  t.log_ctr = c->log_ctr;
+  t.log_cap = c->log_cap;
+  t.horizon = c->horizon;
+  t.hist_lost = c->log_ctr + (size_t)LOG_PARTS * LOG_CTR_STRIDE;
+  t.tear = c->tear;
+  t.log_epoch = nullptr;  // (a batch's: enqueue)
+  t.mask = c->nslots - 1;
+  t.arena = c->arena;
+  t.arena_used16 = c->s[0].counters + 4;
+  t.arena_cap16 = c->arena_cap16;
+  t.max_probe = (uint32_t)std::min<uint64_t>(c->nslots, 1u << 16);
+  t.shift = 64u - (uint32_t)__builtin_ctzll(c->nslots);
+  return t;
+}
+
+Params params(Engine* c, int isolate) {
+  Params P;
+  P.ratio = c->cfg.near_limit_ratio;
+  P.lc_en = c->cfg.local_cache_enabled != 0;
+  P.per_second = c->cfg.per_second_split != 0;
+  P.isolate = isolate;
+  return P;
+}
+
+}  // namespace rl
 
 namespace {
-
-thread_local std::string g_err;
-
-int set_err(Engine* c, int code, const std::string& msg);
 
 // Fold event set k (a timed batch) into the stage sums; waits for the batch.
 void prof_fold(Engine* c, uint32_t k) {
@@ -69,61 +144,8 @@ hipEvent_t* prof_events(Engine* c) {
   return c->ev[k];
 }
 
-int set_err(Engine* c, int code, const std::string& msg) {
-  if (c) c->last_error = msg;
-  else g_err = msg;
-  return code;
-}
-
-#define HIPCHK(c, expr)                                                                        \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess)                                                                      \
-      return set_err((c), RL_E_HIP, std::string("gpu: ") + #expr + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-// Every entry point but the packed request one and eng_batch_progress starts
-// by completing the pending packed request batches (eng_requests_advance).
-#define RQ_SETTLE(c)                                               \
-  do {                                                             \
-    if ((c)->rq_n) {                                               \
-      const int _rc = rl::eng_requests_advance((c), (c)->rq_n);    \
-      if (_rc) return _rc;                                         \
-    }                                                              \
-  } while (0)
-
-template <typename T>
-hipError_t dalloc(T** p, size_t count) {
-  return hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-}
-
 inline double wall_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-int map_err(Engine* c, uint32_t e) {
-  if (!e) return RL_OK;
-  if (e & ERR_TIME) return set_err(c, RL_E_TIME, "gpu: now outside [0, 2^32-172800] or before the last sweep");
-  if (e & ERR_HISTORY)
-    return set_err(c, RL_E_TIME,
-                   "gpu: a request's window is older than its key's history holds (more than 8 windows and "
-                   "div + expiration_jitter_max_seconds behind the key's newest, or the history log overwrote it: "
-                   "raise history_entries)");
-  if (e & ERR_INVALID) return set_err(c, RL_E_INVALID, "gpu: malformed batch (unit, rule id, request index or stem offsets)");
-  if (e & ERR_TABLE_FULL) return set_err(c, RL_E_TABLE_FULL, "gpu: counter table full (raise table_slots or sweep)");
-  if (e & ERR_ARENA_FULL) return set_err(c, RL_E_ARENA_FULL, "gpu: long-stem arena full (raise arena_bytes)");
-  return set_err(c, RL_E_INTERNAL, "gpu: unknown device error");
-}
-
-// Order stream st after every batch submitted so far: each buffer's last
-// batch to its end (a batch's k_finish may still run after the next batch's
-// stage B has started: that waits for b_table only).
-hipError_t after_batches(Engine* c, hipStream_t st) {
-  for (uint32_t k = 0; k < NBUF; k++) {
-    const hipError_t e = hipStreamWaitEvent(st, c->b_done[k], 0);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
 }
 
 // Read (and clear) the sticky device error words; synchronises the stream,
@@ -142,9 +164,6 @@ int collect(Engine* c, hipStream_t st = nullptr) {
   }
   return map_err(c, e);
 }
-
-TableDev table_view(Engine* c);
-Params params(Engine* c, int isolate = 0);
 
 // Enqueue one batch. Pipelined (ctx streams): stage A on the buffer's own
 // stream as soon as the buffer is free, stage B after the previous batch's
@@ -283,48 +302,6 @@ BatchDev dev_view(const Engine* c, const rl_batch* in, uint32_t stem_cap) {
   b.hits = in->hits;
   b.rule = in->rule_id;
   return b;
-}
-
-// The history log's append counters (LOG_PARTS) and its lost-lookup count.
-hipError_t log_ctr_get(Engine* c, std::vector<unsigned long long>& ctr, unsigned long long* lost,
-                       unsigned long long* refused = nullptr) {
-  std::vector<unsigned long long> h((size_t)(LOG_PARTS + 1) * LOG_CTR_STRIDE);
-  hipError_t e = hipMemcpyAsync(h.data(), c->log_ctr, h.size() * 8, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return e;
-  ctr.resize(LOG_PARTS);
-  for (uint32_t k = 0; k < LOG_PARTS; k++) ctr[k] = h[(size_t)k * LOG_CTR_STRIDE];
-  if (lost) *lost = h[(size_t)LOG_PARTS * LOG_CTR_STRIDE];
-  if (refused) *refused = h[(size_t)LOG_PARTS * LOG_CTR_STRIDE + 1];
-  return hipSuccess;
-}
-
-TableDev table_view(Engine* c) {
-  TableDev t;
-  t.slots = c->slots;
-  t.log = c->log;
-  t.log_ctr = c->log_ctr;
-  t.log_cap = c->log_cap;
-  t.horizon = c->horizon;
-  t.hist_lost = c->log_ctr + (size_t)LOG_PARTS * LOG_CTR_STRIDE;
-  t.tear = c->tear;
-  t.log_epoch = nullptr;  // (a batch's: enqueue)
-  t.mask = c->nslots - 1;
-  t.arena = c->arena;
-  t.arena_used16 = c->s[0].counters + 4;
-  t.arena_cap16 = c->arena_cap16;
-  t.max_probe = (uint32_t)std::min<uint64_t>(c->nslots, 1u << 16);
-  t.shift = 64u - (uint32_t)__builtin_ctzll(c->nslots);
-  return t;
-}
-
-Params params(Engine* c, int isolate) {
-  Params P;
-  P.ratio = c->cfg.near_limit_ratio;
-  P.lc_en = c->cfg.local_cache_enabled != 0;
-  P.per_second = c->cfg.per_second_split != 0;
-  P.isolate = isolate;
-  return P;
 }
 
 // Per-batch scratch of one pipeline buffer (sized for max_batch descriptors).
@@ -2889,875 +2866,6 @@ int eng_snapshot_load(Engine* c, const void* host, uint64_t bytes) {
   c->hash_seed = h.hash_seed;
   c->cfg.hash_seed = h.hash_seed;
   c->hk = hash_key_of(h.hash_seed, c->cfg.debug_hash_bits);
-  return RL_OK;
-}
-
-namespace {
-
-// Device memory of one call, freed when it returns.
-struct DevBufs {
-  std::vector<void*> p;
-  ~DevBufs() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  template <typename T>
-  hipError_t get(T** out, size_t count) {
-    const hipError_t e = dalloc(out, count);
-    if (e == hipSuccess) p.push_back(*out);
-    return e;
-  }
-};
-
-}  // namespace
-
-int eng_export_range(Engine* c, uint64_t s0, uint64_t s1, rl_records* out, rl_export_info* info) {
-  if (!c || !info) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  RQ_SETTLE(c);
-  if (out && (!out->stem_off || (out->n && (!out->unit || !out->flags || !out->ws || !out->count || !out->expire ||
-                                            !out->lc)) ||
-              (out->stem_cap && !out->stem_bytes)))
-    return set_err(c, RL_E_INVALID, "gpu: null rl_records array");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream;
-  HIPCHK(c, after_batches(c, st));
-  s1 = std::min<uint64_t>(s1, c->nslots);
-  s0 = std::min(s0, s1);
-  *info = rl_export_info{};
-  info->shard_slots = c->nslots;
-  HIPCHK(c, hipMemcpyAsync(&info->time_floor, c->s[0].time_floor, 8, hipMemcpyDeviceToHost, st));
-  DevBufs mem;
-  uint32_t* cnt = nullptr;
-  unsigned long long* tot = nullptr;  // [0..3] the range's sums, [4] the write cursor
-  unsigned long long h_tot[5] = {};
-  if (s1 > s0) {
-    HIPCHK(c, mem.get(&cnt, s1 - s0));
-    HIPCHK(c, mem.get(&tot, 5));
-    HIPCHK(c, hipMemsetAsync(tot, 0, 40, st));
-    launch_export_count(table_view(c), s0, s1, cnt, tot, st);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h_tot, tot, 40, hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(c, hipStreamSynchronize(st));
-  const uint64_t nrec = h_tot[0], nb = h_tot[1];
-  info->records = nrec;
-  info->stem_bytes = nb;
-  info->keys = h_tot[2];
-  info->chains_lost = h_tot[3];
-  if (!out) return RL_OK;
-  // (stem_off is 32-bit per call: a range holding 4 GiB of stems goes out in smaller ranges)
-  if (nrec > out->n || nb > out->stem_cap || nb > 0xFFFFFFFFull)
-    return set_err(c, RL_E_CAPACITY,
-                   "gpu: export range holds " + std::to_string(nrec) + " records / " + std::to_string(nb) +
-                       " stem bytes: larger than rl_records (or 4 GiB of stems: export smaller ranges)");
-  out->n = (uint32_t)nrec;
-  out->stem_off[0] = 0;
-  if (!nrec) return RL_OK;
-  ExportDev o{};
-  HIPCHK(c, mem.get(&o.stem, nb));
-  HIPCHK(c, mem.get(&o.off, nrec));
-  HIPCHK(c, mem.get(&o.unit, nrec));
-  HIPCHK(c, mem.get(&o.flags, nrec));
-  HIPCHK(c, mem.get(&o.ws, nrec));
-  HIPCHK(c, mem.get(&o.count, nrec));
-  HIPCHK(c, mem.get(&o.expire, nrec));
-  HIPCHK(c, mem.get(&o.lc, nrec));
-  launch_export_write(table_view(c), s0, s1, cnt, tot + 4, o, st);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out->stem_bytes, o.stem, nb, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(out->stem_off, o.off, nrec * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(out->unit, o.unit, nrec, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(out->flags, o.flags, nrec, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(out->ws, o.ws, nrec * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(out->count, o.count, nrec * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(out->expire, o.expire, nrec * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(out->lc, o.lc, nrec * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(h_tot + 4, tot + 4, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  out->stem_off[nrec] = (uint32_t)nb;
-  if (h_tot[4] != ((nrec << 32) | nb)) return set_err(c, RL_E_INTERNAL, "gpu: export wrote other than it counted");
-  return RL_OK;
-}
-
-int eng_hot_check(Engine* c, const rl_hot_query* q) {
-  if (!c || !q) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  if (q->flags & ~RL_HOT_BLOCKED) return set_err(c, RL_E_INVALID, "gpu: rl_hot_keys: unknown flags");
-  if (q->unit_mask & ~rlhot::UNIT_BITS) return set_err(c, RL_E_INVALID, "gpu: rl_hot_keys: unit_mask bit outside 1..4");
-  if ((q->flags & RL_HOT_BLOCKED) && !c->cfg.local_cache_enabled)
-    return set_err(c, RL_E_INVALID, "gpu: rl_hot_keys: RL_HOT_BLOCKED on a ctx without local cache");
-  if (q->k > c->cfg.max_batch) return set_err(c, RL_E_CAPACITY, "gpu: rl_hot_keys: k exceeds configured max_batch");
-  if (q->now < 0 || q->now > (int64_t)NOW_MAX) return set_err(c, RL_E_TIME, "gpu: now out of range");
-  return RL_OK;
-}
-
-int eng_hot_keys(Engine* c, const rl_hot_query* q, HotAnswer* ans, rl_hot_info* info) {
-  if (!c || !q || !ans || !info) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  if (const int rc = eng_hot_check(c, q)) return rc;
-  RQ_SETTLE(c);
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream;
-  HIPCHK(c, after_batches(c, st));
-  int64_t floor = 0;
-  HIPCHK(c, hipMemcpyAsync(&floor, c->s[0].time_floor, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (q->now < floor) return set_err(c, RL_E_TIME, "gpu: now below the sweep floor");
-  const uint32_t k = q->k;
-  const uint64_t range = std::min<uint64_t>(c->hot_range, c->nslots);
-  const uint64_t pool_cap = k ? range + 2ull * k : 0;  // (< 2^32: range <= 2^22, k <= max_batch <= 2^23)
-  const rlhot::Query dq{(uint32_t)q->now, q->min_count, q->unit_mask, q->flags};
-  DevBufs mem;
-  HotState* hs = nullptr;
-  unsigned long long* pool = nullptr;
-  HIPCHK(c, mem.get(&hs, 1));
-  if (k) HIPCHK(c, mem.get(&pool, pool_cap));
-  HIPCHK(c, hipMemsetAsync(hs, 0, sizeof(HotState), st));
-  const TableDev t = table_view(c);
-  // The ranges start small and double up to `range`: the first cut then runs
-  // on a pool of a few K entries, not on every match of 2^22 slots (one
-  // workgroup selects), and with its threshold the later ranges add little.
-  for (uint64_t s0 = 0, r = std::min<uint64_t>(range, 4096); s0 < c->nslots; r = std::min(2 * r, range)) {
-    const uint64_t s1 = std::min(s0 + r, c->nslots);
-    launch_hot_scan(t, s0, s1, dq, k, hs, pool, (uint32_t)pool_cap, st);
-    if (k) launch_hot_select(hs, pool, (uint32_t)pool_cap, k, 2 * k, st);
-    s0 = s1;
-  }
-  if (k) {
-    launch_hot_select(hs, pool, (uint32_t)pool_cap, k, k, st);
-    launch_hot_size(t, hs, pool, (uint32_t)pool_cap, k, st);
-  }
-  HIPCHK(c, hipGetLastError());
-  HotState h{};
-  HIPCHK(c, hipMemcpyAsync(&h, hs, sizeof h, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (h.err || h.pool_n > k) return set_err(c, RL_E_INTERNAL, "gpu: rl_hot_keys: the candidate pool overflowed");
-  *info = rl_hot_info{};
-  info->slots = c->nslots;
-  info->matched = h.matched;
-  info->hits = h.hits;
-  info->time_floor = floor;
-  const uint32_t n = h.pool_n;
-  const uint64_t nb = h.stem_bytes;
-  *ans = HotAnswer{};
-  if (!n) return RL_OK;
-  HotOutDev o{};
-  o.stem_cap = nb;
-  HIPCHK(c, mem.get(&o.stem, nb));
-  HIPCHK(c, mem.get(&o.off, n));
-  HIPCHK(c, mem.get(&o.len, n));
-  HIPCHK(c, mem.get(&o.unit, n));
-  HIPCHK(c, mem.get(&o.ws, n));
-  HIPCHK(c, mem.get(&o.count, n));
-  HIPCHK(c, mem.get(&o.expire, n));
-  HIPCHK(c, mem.get(&o.lc, n));
-  launch_hot_gather(t, hs, pool, n, o, st);
-  HIPCHK(c, hipGetLastError());
-  ans->stem.resize(nb);
-  ans->unit.resize(n);
-  for (std::vector<uint32_t>* v : {&ans->off, &ans->len, &ans->ws, &ans->count, &ans->expire, &ans->lc}) v->resize(n);
-  HIPCHK(c, hipMemcpyAsync(ans->stem.data(), o.stem, nb, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(ans->off.data(), o.off, n * 4ull, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(ans->len.data(), o.len, n * 4ull, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(ans->unit.data(), o.unit, n, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(ans->ws.data(), o.ws, n * 4ull, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(ans->count.data(), o.count, n * 4ull, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(ans->expire.data(), o.expire, n * 4ull, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(ans->lc.data(), o.lc, n * 4ull, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(&h, hs, sizeof h, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (h.err || h.cursor != nb) return set_err(c, RL_E_INTERNAL, "gpu: rl_hot_keys gathered other than it sized");
-  return RL_OK;
-}
-
-int eng_scan_check(Engine* c, const rl_scan_query* q, const rl_records* out) {
-  if (!c || !q) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  if (q->flags & ~(RL_SCAN_NEWEST | RL_SCAN_LIVE)) return set_err(c, RL_E_INVALID, "gpu: rl_scan: unknown flags");
-  if (q->reserved) return set_err(c, RL_E_INVALID, "gpu: rl_scan: reserved field not zero");
-  if (q->unit_mask & ~rlhot::UNIT_BITS) return set_err(c, RL_E_INVALID, "gpu: rl_scan: unit_mask bit outside 1..4");
-  const uint32_t n = q->n_prefixes;
-  if (n > RL_FORGET_PREFIX_MAX) return set_err(c, RL_E_CAPACITY, "gpu: rl_scan: more than RL_FORGET_PREFIX_MAX prefixes");
-  if (n) {
-    if (!q->prefix_bytes || !q->prefix_off) return set_err(c, RL_E_INVALID, "gpu: rl_scan: null prefix array");
-    if (q->prefix_off[0] != 0) return set_err(c, RL_E_INVALID, "gpu: rl_scan prefix offsets must start at 0");
-    for (uint32_t i = 0; i < n; i++)
-      if (q->prefix_off[i + 1] <= q->prefix_off[i])  // (no empty prefix: n_prefixes == 0 is "every key")
-        return set_err(c, RL_E_INVALID, "gpu: rl_scan prefix " + std::to_string(i) + ": empty, or offsets decrease");
-    if (q->prefix_off[n] > RL_FORGET_PREFIX_BYTES)
-      return set_err(c, RL_E_CAPACITY, "gpu: rl_scan: more than RL_FORGET_PREFIX_BYTES bytes of prefixes");
-  }
-  if ((q->flags & RL_SCAN_LIVE) && (q->now < 0 || q->now > (int64_t)NOW_MAX))
-    return set_err(c, RL_E_TIME, "gpu: now out of range");
-  if (out && (!out->stem_off || (out->n && (!out->unit || !out->flags || !out->ws || !out->count || !out->expire ||
-                                            !out->lc)) ||
-              (out->stem_cap && !out->stem_bytes)))
-    return set_err(c, RL_E_INVALID, "gpu: null rl_records array");
-  return RL_OK;
-}
-
-namespace {
-
-// device staging that lives with the engine: at least `need` elements, never shrunk
-template <typename T>
-hipError_t scan_grow(T** p, size_t* cap, size_t need) {
-  if (need <= *cap) return hipSuccess;
-  const size_t want = std::max(need, *cap + *cap / 2);
-  T* q = nullptr;
-  const hipError_t e = dalloc(&q, want);
-  if (e != hipSuccess) return e;
-  if (*p) (void)hipFree(*p);
-  *p = q;
-  *cap = want;
-  return hipSuccess;
-}
-
-}  // namespace
-
-int eng_scan(Engine* c, const rl_scan_query* q, uint64_t* slot, rl_records* out, rl_scan_prefix_sum* by_prefix,
-             rl_scan_info* info) {
-  if (!c || !slot) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  if (const int rc = eng_scan_check(c, q, out)) return rc;
-  if (*slot % RL_SCAN_TILE || *slot > c->nslots)
-    return set_err(c, RL_E_INVALID, "gpu: rl_scan: cursor slot is no multiple of RL_SCAN_TILE, or beyond the shard");
-  RQ_SETTLE(c);
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream;
-  HIPCHK(c, after_batches(c, st));  // (the staging below is this synchronous call's own)
-  Engine::ScanStage& S = c->scan;
-  if (!S.pfx) {
-    HIPCHK(c, dalloc(&S.pfx, (size_t)RL_FORGET_PREFIX_BYTES));
-    HIPCHK(c, dalloc(&S.poff, (size_t)RL_FORGET_PREFIX_MAX + 1));
-    HIPCHK(c, dalloc(&S.byp, (size_t)RL_FORGET_PREFIX_MAX * 3 + 1));
-    HIPCHK(c, hipMemsetAsync(S.pfx, 0, RL_FORGET_PREFIX_BYTES, st));
-    HIPCHK(c, hipMemsetAsync(S.poff, 0, (RL_FORGET_PREFIX_MAX + 1) * 4, st));
-  }
-  int64_t floor = 0;
-  HIPCHK(c, hipMemcpyAsync(&floor, c->s[0].time_floor, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if ((q->flags & RL_SCAN_LIVE) && q->now < floor) return set_err(c, RL_E_TIME, "gpu: now below the sweep floor");
-  const uint32_t np = q->n_prefixes, nbins = std::max(np, 1u);
-  if (np) {
-    HIPCHK(c, hipMemcpyAsync(S.pfx, q->prefix_bytes, q->prefix_off[np], hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(S.poff, q->prefix_off, ((size_t)np + 1) * 4, hipMemcpyHostToDevice, st));
-  }
-  HIPCHK(c, hipMemsetAsync(S.byp, 0, ((size_t)RL_FORGET_PREFIX_MAX * 3 + 1) * 8, st));
-  uint32_t* d_err = reinterpret_cast<uint32_t*>(S.byp + RL_FORGET_PREFIX_MAX * 3);
-  const ScanQueryDev dq{S.pfx, S.poff, np, q->flags, (q->flags & RL_SCAN_LIVE) ? (uint32_t)q->now : 0u, q->unit_mask};
-  const TableDev t = table_view(c);
-  const uint64_t total = rlscan::tiles_of(c->nslots), first = *slot / RL_SCAN_TILE;
-  rl_scan_info sum{};
-  sum.time_floor = floor;
-  std::vector<rlscan::TileSum> h_sums;
-  std::vector<uint64_t> h_base;
-  auto slots_of = [&](uint64_t t0, uint64_t t1) {  // slots of the tiles [t0, t1)
-    return std::min(t1 * RL_SCAN_TILE, c->nslots) - std::min(t0 * RL_SCAN_TILE, c->nslots);
-  };
-  uint64_t tile = first;
-  if (!out) {
-    // count only: one pass over the rest of the shard, which it covers whole
-    for (; tile < total;) {
-      const uint32_t nt = (uint32_t)std::min<uint64_t>(total - tile, 1u << 20);
-      HIPCHK(c, scan_grow(&S.sums, &S.tile_cap, nt));
-      launch_scan_count(t, c->nslots, tile, nt, dq, nullptr, S.sums, S.byp, st);
-      HIPCHK(c, hipGetLastError());
-      h_sums.resize(nt);
-      HIPCHK(c, hipMemcpyAsync(h_sums.data(), S.sums, (size_t)nt * sizeof(rlscan::TileSum), hipMemcpyDeviceToHost, st));
-      HIPCHK(c, hipStreamSynchronize(st));
-      for (const rlscan::TileSum& x : h_sums) {  // (no cut: a count has no 32-bit offsets to respect)
-        sum.records += x.records;
-        sum.stem_bytes += x.bytes;
-        sum.keys += x.keys;
-        sum.chains_lost += x.lost;
-      }
-      tile += nt;
-    }
-  } else {
-    const uint64_t rec_cap = out->n, byte_cap = std::min<uint64_t>(out->stem_cap, rlscan::BYTES_MAX);
-    // The spans start small and double: a small page then counts a few tiles,
-    // not 2^22 slots, and a large one (the first span: as many tiles as the
-    // page has records per RL_SCAN_TILE) is soon at full width.
-    const uint32_t span0 = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(16, rec_cap / RL_SCAN_TILE), c->scan_span);
-    for (uint32_t span = span0; tile < total; span = std::min(2 * span, c->scan_span)) {
-      const uint32_t nt = (uint32_t)std::min<uint64_t>(total - tile, span);
-      HIPCHK(c, scan_grow(&S.sums, &S.tile_cap, nt));
-      HIPCHK(c, scan_grow(&S.cnt, &S.cnt_cap, (size_t)nt * RL_SCAN_TILE));
-      launch_scan_count(t, c->nslots, tile, nt, dq, S.cnt, S.sums, nullptr, st);
-      HIPCHK(c, hipGetLastError());
-      h_sums.resize(nt);
-      h_base.resize(nt);
-      HIPCHK(c, hipMemcpyAsync(h_sums.data(), S.sums, (size_t)nt * sizeof(rlscan::TileSum), hipMemcpyDeviceToHost, st));
-      HIPCHK(c, hipStreamSynchronize(st));
-      const rlscan::Cut cut =
-          rlscan::plan(h_sums.data(), nt, rec_cap - sum.records, byte_cap - sum.stem_bytes, h_base.data());
-      if (!cut.tiles && tile == first) {
-        if (info) {
-          *info = rl_scan_info{};
-          info->need_records = h_sums[0].records;
-          info->need_stem_bytes = h_sums[0].bytes;
-          info->time_floor = floor;
-        }
-        return set_err(c, RL_E_CAPACITY,
-                       "gpu: rl_scan: the first tile holds " + std::to_string(h_sums[0].records) + " records / " +
-                           std::to_string(h_sums[0].bytes) + " stem bytes: larger than rl_records");
-      }
-      if (cut.records) {
-        const uint64_t nrec = cut.records, nb = cut.bytes;
-        HIPCHK(c, scan_grow(&S.base, &S.base_cap, cut.tiles));
-        if (nrec > S.rec_cap) {  // (the seven record arrays grow together)
-          size_t caps[7];
-          for (size_t& x : caps) x = S.rec_cap;
-          HIPCHK(c, scan_grow(&S.o.off, &caps[0], nrec));
-          HIPCHK(c, scan_grow(&S.o.unit, &caps[1], caps[0]));
-          HIPCHK(c, scan_grow(&S.o.flags, &caps[2], caps[0]));
-          HIPCHK(c, scan_grow(&S.o.ws, &caps[3], caps[0]));
-          HIPCHK(c, scan_grow(&S.o.count, &caps[4], caps[0]));
-          HIPCHK(c, scan_grow(&S.o.expire, &caps[5], caps[0]));
-          HIPCHK(c, scan_grow(&S.o.lc, &caps[6], caps[0]));
-          S.rec_cap = caps[0];
-        }
-        HIPCHK(c, scan_grow(&S.o.stem, &S.byte_cap, nb));
-        HIPCHK(c, hipMemcpyAsync(S.base, h_base.data(), (size_t)cut.tiles * 8, hipMemcpyHostToDevice, st));
-        launch_scan_write(t, c->nslots, tile, cut.tiles, dq, S.cnt, S.base, (uint32_t)sum.stem_bytes, S.o, (uint32_t)nrec,
-                          (uint32_t)nb, S.byp, d_err, st);
-        HIPCHK(c, hipGetLastError());
-        const uint64_t r0 = sum.records;
-        HIPCHK(c, hipMemcpyAsync(out->stem_bytes + sum.stem_bytes, S.o.stem, nb, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(out->stem_off + r0, S.o.off, nrec * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(out->unit + r0, S.o.unit, nrec, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(out->flags + r0, S.o.flags, nrec, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(out->ws + r0, S.o.ws, nrec * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(out->count + r0, S.o.count, nrec * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(out->expire + r0, S.o.expire, nrec * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(out->lc + r0, S.o.lc, nrec * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));  // (h_base and the staging are free again)
-      }
-      sum.records += cut.records;
-      sum.stem_bytes += cut.bytes;
-      sum.keys += cut.keys;
-      sum.chains_lost += cut.lost;
-      tile += cut.tiles;
-      if (cut.tiles < nt) break;  // the next tile does not fit: the page is full
-    }
-  }
-  unsigned long long h_byp[RL_FORGET_PREFIX_MAX * 3 + 1] = {};
-  HIPCHK(c, hipMemcpyAsync(h_byp, S.byp, sizeof h_byp, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  uint64_t byp_records = 0;
-  for (uint32_t p = 0; p < nbins; p++) byp_records += h_byp[p * 3 + 1];
-  if ((uint32_t)h_byp[RL_FORGET_PREFIX_MAX * 3] || byp_records != sum.records)
-    return set_err(c, RL_E_INTERNAL, "gpu: rl_scan wrote other than it counted");
-  sum.slots_scanned = slots_of(first, tile);
-  if (out) {
-    out->n = (uint32_t)sum.records;
-    out->stem_off[0] = 0;
-    out->stem_off[sum.records] = (uint32_t)sum.stem_bytes;
-  }
-  if (by_prefix)
-    for (uint32_t p = 0; p < nbins; p++) by_prefix[p] = rl_scan_prefix_sum{h_byp[p * 3], h_byp[p * 3 + 1], h_byp[p * 3 + 2]};
-  if (info) *info = sum;
-  *slot = std::min(tile * RL_SCAN_TILE, c->nslots);
-  return RL_OK;
-}
-
-int eng_import_check(Engine* c, const rl_records* in) {
-  if (!c || !in) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  const uint32_t n = in->n;
-  if (n > c->cfg.max_batch) return set_err(c, RL_E_CAPACITY, "gpu: import exceeds configured max_batch");
-  if (!n) return RL_OK;
-  if (!in->stem_bytes || !in->stem_off || !in->unit || !in->ws || !in->count || !in->expire || !in->lc)
-    return set_err(c, RL_E_INVALID, "gpu: null rl_records array");
-  if (in->stem_off[0] != 0) return set_err(c, RL_E_INVALID, "gpu: import stem offsets must start at 0");
-  for (uint32_t i = 0; i < n; i++) {
-    const uint32_t a = in->stem_off[i], b = in->stem_off[i + 1];
-    if (b <= a || b - a > 65535u)
-      return set_err(c, RL_E_INVALID, "gpu: import record " + std::to_string(i) + ": stem offsets (1..65535 bytes)");
-    const uint32_t u = in->unit[i];
-    if (u < 1 || u > 4) return set_err(c, RL_E_INVALID, "gpu: import record " + std::to_string(i) + ": unit outside 1..4");
-    if (in->ws[i] > NOW_MAX || in->ws[i] % div_of(u))
-      return set_err(c, RL_E_INVALID,
-                     "gpu: import record " + std::to_string(i) + ": ws is no window start of its unit (or > 2^32-172801)");
-  }
-  if (in->stem_off[n] > c->cfg.max_stem_bytes)
-    return set_err(c, RL_E_CAPACITY, "gpu: import exceeds configured max_stem_bytes");
-  return RL_OK;
-}
-
-int eng_import(Engine* c, const rl_records* in) {
-  if (const int rc = eng_import_check(c, in)) return rc;
-  RQ_SETTLE(c);
-  const uint32_t n = in->n;
-  if (!n) return RL_OK;
-  // group the records by stem (a stem's records stay in arrival order): one
-  // lane of k_import takes a stem with all its units
-  std::vector<uint64_t> hash(n);
-  for (uint32_t i = 0; i < n; i++) {
-    uint64_t h = hash_stem_host(c->hk, in->stem_bytes + in->stem_off[i], in->stem_off[i + 1] - in->stem_off[i]);
-    if ((uint32_t)(h >> 32) == KEY_DUP) h = ((uint64_t)(KEY_DUP - 1u) << 32) | (uint32_t)h;  // (as k_prepare homes it)
-    hash[i] = h;
-  }
-  auto stem_cmp = [&](uint32_t x, uint32_t y) {
-    const uint32_t lx = in->stem_off[x + 1] - in->stem_off[x], ly = in->stem_off[y + 1] - in->stem_off[y];
-    if (lx != ly) return lx < ly ? -1 : 1;
-    return memcmp(in->stem_bytes + in->stem_off[x], in->stem_bytes + in->stem_off[y], lx);
-  };
-  std::vector<uint32_t> order(n);
-  for (uint32_t i = 0; i < n; i++) order[i] = i;
-  std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-    if (hash[x] != hash[y]) return hash[x] < hash[y];
-    const int k = stem_cmp(x, y);
-    return k ? k < 0 : x < y;
-  });
-  std::vector<ImportRec> rec(n);
-  std::vector<uint32_t> gstart;
-  std::vector<unsigned long long> ghash;
-  for (uint32_t j = 0; j < n; j++) {
-    const uint32_t i = order[j];
-    if (!j || hash[i] != hash[order[j - 1]] || stem_cmp(i, order[j - 1])) {
-      gstart.push_back(j);
-      ghash.push_back(hash[i]);
-    }
-    ImportRec& r = rec[j];
-    r.off = in->stem_off[i];
-    r.lu = (in->stem_off[i + 1] - in->stem_off[i]) | ((uint32_t)in->unit[i] << 16) |
-           ((uint32_t)((in->flags ? in->flags[i] : 0) & RL_REC_CHAIN_LOST) << 24);
-    r.ws = in->ws[i];
-    r.count = in->count[i];
-    r.expire = in->expire[i];
-    r.lc = in->lc[i];
-    r.pad[0] = r.pad[1] = 0;
-  }
-  gstart.push_back(n);
-  const uint32_t ng = (uint32_t)ghash.size(), nb = in->stem_off[n];
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream;
-  HIPCHK(c, after_batches(c, st));
-  DevBufs mem;
-  uint8_t* d_stem = nullptr;
-  ImportRec* d_rec = nullptr;
-  uint32_t *d_gs = nullptr, *d_err = nullptr;
-  unsigned long long *d_gh = nullptr, *d_epoch = nullptr;
-  HIPCHK(c, mem.get(&d_stem, (size_t)nb + 64));
-  HIPCHK(c, mem.get(&d_rec, n));
-  HIPCHK(c, mem.get(&d_gs, (size_t)ng + 1));
-  HIPCHK(c, mem.get(&d_gh, ng));
-  HIPCHK(c, mem.get(&d_epoch, LOG_PARTS));
-  HIPCHK(c, mem.get(&d_err, 1));
-  HIPCHK(c, hipMemcpyAsync(d_stem, in->stem_bytes, nb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_rec, rec.data(), (size_t)n * sizeof(ImportRec), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_gs, gstart.data(), ((size_t)ng + 1) * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(d_gh, ghash.data(), (size_t)ng * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemsetAsync(d_err, 0, 4, st));
-  launch_import(table_view(c), c->hk, d_stem, nb, d_rec, d_gs, d_gh, ng, d_epoch, d_err, st);
-  HIPCHK(c, hipGetLastError());
-  uint32_t e = 0;
-  HIPCHK(c, hipMemcpyAsync(&e, d_err, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return map_err(c, e);
-}
-
-int eng_lookup_check(Engine* c, const rl_keys* in, const rl_key_state* out) {
-  if (!c || !in || !out) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  const uint32_t n = in->n;
-  if (n > c->cfg.max_batch) return set_err(c, RL_E_CAPACITY, "gpu: lookup exceeds configured max_batch");
-  if (!n) return RL_OK;
-  if (!in->stem_bytes || !in->stem_off || !in->unit || !in->now)
-    return set_err(c, RL_E_INVALID, "gpu: null rl_keys array");
-  if (!out->status || !out->found || !out->count || !out->expire || !out->lc)
-    return set_err(c, RL_E_INVALID, "gpu: null rl_key_state array");
-  if (in->stem_off[0] != 0) return set_err(c, RL_E_INVALID, "gpu: lookup stem offsets must start at 0");
-  for (uint32_t i = 0; i < n; i++)  // (an empty or over-long stem is that key's own status)
-    if (in->stem_off[i + 1] < in->stem_off[i])
-      return set_err(c, RL_E_INVALID, "gpu: lookup key " + std::to_string(i) + ": stem offsets decrease");
-  if (in->stem_off[n] > c->cfg.max_stem_bytes)
-    return set_err(c, RL_E_CAPACITY, "gpu: lookup exceeds configured max_stem_bytes");
-  return RL_OK;
-}
-
-int eng_lookup(Engine* c, const rl_keys* in, rl_key_state* out) {
-  if (const int rc = eng_lookup_check(c, in, out)) return rc;
-  RQ_SETTLE(c);
-  const uint32_t n = in->n;
-  if (!n) return RL_OK;
-  const uint32_t nb = in->stem_off[n];
-  std::vector<uint32_t> now32(n);  // the clocks as the table keeps them
-  for (uint32_t i = 0; i < n; i++)
-    now32[i] = in->now[i] < 0 || in->now[i] > (int64_t)NOW_MAX ? LOOKUP_NOW_BAD : (uint32_t)in->now[i];
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream;
-  HIPCHK(c, after_batches(c, st));  // (the staging below is the synchronous entry points': free by then)
-  if (nb) HIPCHK(c, hipMemcpyAsync(c->d_stem, in->stem_bytes, nb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->d_off, in->stem_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->d_unit, in->unit, n, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(c->d_req, now32.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-  const LookupDev q{n, c->d_off, c->d_unit, c->d_req, c->d_status, c->d_code, c->d_rem, c->d_reset, c->d_limit};
-  launch_lookup(table_view(c), c->hk, params(c), c->s[0].time_floor, c->d_stem, nb, q, st);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out->status, q.status, n, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(out->found, q.found, n, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(out->count, q.count, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(out->expire, q.expire, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(out->lc, q.lc, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));  // (now32 lives until here)
-  return RL_OK;
-}
-
-int eng_forget_check(Engine* c, const rl_stems* in) {
-  if (!c || !in) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  if (in->flags & ~(RL_FORGET_PREFIX | RL_FORGET_DRY_RUN)) return set_err(c, RL_E_INVALID, "gpu: rl_forget: unknown flags");
-  const bool prefix = in->flags & RL_FORGET_PREFIX;
-  const uint32_t n = in->n;
-  if (prefix ? n > RL_FORGET_PREFIX_MAX : n > c->cfg.max_batch)
-    return set_err(c, RL_E_CAPACITY, prefix ? "gpu: rl_forget: more than RL_FORGET_PREFIX_MAX prefixes"
-                                            : "gpu: rl_forget exceeds configured max_batch");
-  if (!n) return RL_OK;
-  if (!in->stem_bytes || !in->stem_off) return set_err(c, RL_E_INVALID, "gpu: null rl_stems array");
-  if (in->stem_off[0] != 0) return set_err(c, RL_E_INVALID, "gpu: rl_forget stem offsets must start at 0");
-  for (uint32_t i = 0; i < n; i++) {
-    const uint32_t a = in->stem_off[i], b = in->stem_off[i + 1];
-    if (b <= a || b - a > 65535u)  // (no empty prefix either: there is no "flush everything")
-      return set_err(c, RL_E_INVALID, "gpu: rl_forget entry " + std::to_string(i) + ": stem offsets (1..65535 bytes)");
-  }
-  if (in->stem_off[n] > (prefix ? RL_FORGET_PREFIX_BYTES : c->cfg.max_stem_bytes))
-    return set_err(c, RL_E_CAPACITY, prefix ? "gpu: rl_forget: more than RL_FORGET_PREFIX_BYTES bytes of prefixes"
-                                            : "gpu: rl_forget exceeds configured max_stem_bytes");
-  return RL_OK;
-}
-
-int eng_forget(Engine* c, const rl_stems* in, uint32_t* removed, rl_forget_info* info) {
-  if (const int rc = eng_forget_check(c, in)) return rc;
-  RQ_SETTLE(c);
-  if (info) *info = rl_forget_info{};
-  const uint32_t n = in->n;
-  if (!n) return RL_OK;
-  const uint32_t nb = in->stem_off[n];
-  const bool prefix = in->flags & RL_FORGET_PREFIX;
-  const uint32_t dry = in->flags & RL_FORGET_DRY_RUN ? 1u : 0u;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream;
-  HIPCHK(c, after_batches(c, st));  // (the staging below is the synchronous entry points': free by then)
-  unsigned long long* ctr = c->s[0].counters;  // (words 0..2: scratch of the synchronous calls, as rl_sweep's)
-  HIPCHK(c, hipMemsetAsync(ctr, 0, 24, st));
-  DevBufs mem;
-  uint32_t* d_removed = c->d_rem;
-  if (prefix) {
-    uint8_t* d_pfx = nullptr;
-    uint32_t* d_poff = nullptr;
-    HIPCHK(c, mem.get(&d_pfx, (size_t)RL_FORGET_PREFIX_BYTES));
-    HIPCHK(c, mem.get(&d_poff, (size_t)RL_FORGET_PREFIX_MAX + 1));
-    HIPCHK(c, mem.get(&d_removed, (size_t)RL_FORGET_PREFIX_MAX));
-    HIPCHK(c, hipMemsetAsync(d_pfx, 0, RL_FORGET_PREFIX_BYTES, st));
-    HIPCHK(c, hipMemsetAsync(d_removed, 0, RL_FORGET_PREFIX_MAX * 4, st));
-    HIPCHK(c, hipMemcpyAsync(d_pfx, in->stem_bytes, nb, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_poff, in->stem_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));
-    launch_forget_scan(table_view(c), c->nslots, d_pfx, d_poff, n, dry, ctr, d_removed, st);
-  } else {
-    uint32_t* claim = nullptr;
-    if (dry) {  // one bit per slot, for this call only: a dry run claims there what the real call claims in the tags
-      const size_t words = (size_t)((c->nslots + 31) / 32);
-      HIPCHK(c, mem.get(&claim, words));
-      HIPCHK(c, hipMemsetAsync(claim, 0, words * 4, st));
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_stem, in->stem_bytes, nb, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->d_off, in->stem_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));
-    const ForgetDev q{n, c->d_off, d_removed, ctr, claim, dry};
-    launch_forget_keys(table_view(c), c->hk, c->d_stem, nb, q, st);
-  }
-  HIPCHK(c, hipGetLastError());
-  unsigned long long h[3] = {};
-  HIPCHK(c, hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
-  if (removed) HIPCHK(c, hipMemcpyAsync(removed, d_removed, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (!dry && h[2]) c->arena_forgotten = true;
-  if (info) {
-    info->slots_scanned = prefix ? c->nslots : 0;
-    info->keys = h[0];
-    info->keys_with_history = h[1];
-    info->arena_bytes = h[2] * 16;
-  }
-  return RL_OK;
-}
-
-// ---------------------------------------------------------------------------
-// rl_resize on one engine, in two steps so that a multi-shard ctx commits only
-// once every shard has placed its keys. eng_resize_place drains the pipeline,
-// allocates and zeroes the new table and runs the placement scan, which only
-// reads the old table: whatever it returns but RL_OK, the engine is as it was
-// and the plan is empty. eng_resize_commit re-points the history log (the one
-// step that writes shared state in place), swaps slots / nslots and frees the
-// old table; eng_resize_abort drops a placed plan instead.
-// ---------------------------------------------------------------------------
-void eng_resize_abort(Engine* c, ResizePlan* p) {
-  if (!p) return;
-  if (c && (p->slots || p->map || p->ctr)) (void)hipSetDevice(c->cfg.device);
-  if (p->slots) (void)hipFree(p->slots);
-  if (p->map) (void)hipFree(p->map);
-  if (p->ctr) (void)hipFree(p->ctr);
-  *p = ResizePlan{};
-}
-
-int eng_resize_check(Engine* c, uint64_t table_slots) {
-  if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
-  if (table_slots < 2 || (table_slots & (table_slots - 1)) || table_slots > (1ull << 32))
-    return set_err(c, RL_E_INVALID, "gpu: rl_resize: table_slots must be a power of two in [2, 2^32]");
-  return RL_OK;
-}
-
-int eng_resize_place(Engine* c, uint64_t table_slots, ResizePlan* p) {
-  if (!p) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  *p = ResizePlan{};
-  if (const int rc = eng_resize_check(c, table_slots)) return rc;
-  RQ_SETTLE(c);
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream;
-  HIPCHK(c, after_batches(c, st));
-  hipError_t e = dalloc(&p->slots, table_slots);
-  if (e == hipSuccess) e = dalloc(&p->map, c->nslots);
-  if (e == hipSuccess) e = dalloc(&p->ctr, RESIZE_CTR_WORDS);
-  if (e == hipSuccess) e = hipMemsetAsync(p->slots, 0, table_slots * sizeof(Slot), st);
-  if (e == hipSuccess) e = hipMemsetAsync(p->ctr, 0, RESIZE_CTR_WORDS * 8, st);
-  unsigned long long h[RESIZE_CTR_WORDS] = {};
-  if (e == hipSuccess) {
-    launch_resize_place(table_view(c), c->hk, c->nslots, p->slots, table_slots, p->map, p->ctr, st);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h, p->ctr, sizeof(h), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();  // (an allocation that failed is this call's error, not the next one's)
-    eng_resize_abort(c, p);
-    return set_err(c, RL_E_HIP, std::string("gpu: rl_resize: ") + hipGetErrorString(e) +
-                                    " (the old and the new table coexist during the call)");
-  }
-  if (h[2]) {
-    eng_resize_abort(c, p);
-    return set_err(c, RL_E_INTERNAL, "gpu: rl_resize: " + std::to_string(h[2]) +
-                                         " live slots whose stem does not hash to their tag and place");
-  }
-  if (h[3]) {
-    eng_resize_abort(c, p);
-    return set_err(c, RL_E_TABLE_FULL, "gpu: rl_resize: " + std::to_string(h[3]) + " of " + std::to_string(h[0] + h[3]) +
-                                           " keys find no free slot within their probe window of a table of " +
-                                           std::to_string(table_slots) + " slots");
-  }
-  p->nslots = table_slots;
-  p->info.slots_before = c->nslots;
-  p->info.slots_after = table_slots;
-  p->info.keys = h[0];
-  p->info.tombstones_dropped = h[1];
-  p->info.longest_probe = (uint32_t)h[4];
-  return RL_OK;
-}
-
-int eng_resize_commit(Engine* c, ResizePlan* p) {
-  if (!c || !p || !p->slots) return set_err(c, RL_E_INVALID, "gpu: rl_resize: nothing placed");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream;
-  unsigned long long relinked = 0;
-  launch_resize_relink(table_view(c), c->nslots, p->map, p->ctr, st);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(&relinked, p->ctr + 5, 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {  // (a failed kernel: the device's state is lost either way)
-    eng_resize_abort(c, p);
-    return set_err(c, RL_E_HIP, std::string("gpu: rl_resize: re-link: ") + hipGetErrorString(e));
-  }
-  p->info.log_entries_relinked = relinked;
-  std::swap(c->slots, p->slots);  // (the plan now holds the old table: freed below)
-  c->nslots = p->nslots;
-  c->cfg.table_slots = p->nslots;
-  const rl_resize_info info = p->info;
-  eng_resize_abort(c, p);
-  p->info = info;
-  return RL_OK;
-}
-
-int eng_resize(Engine* c, uint64_t table_slots, rl_resize_info* info) {
-  ResizePlan p;
-  if (const int rc = eng_resize_place(c, table_slots, &p)) return rc;
-  if (const int rc = eng_resize_commit(c, &p)) return rc;
-  if (info) *info = p.info;
-  return RL_OK;
-}
-
-// ---------------------------------------------------------------------------
-// rl_resize_history on one engine, in rl_resize's two steps. eng_relog_place
-// drains the pipeline, allocates the new log and the head map and runs the
-// placement, which only reads the table and the old log: whatever it returns
-// but RL_OK, the engine is as it was and the plan is empty. eng_relog_commit
-// stores the new chain heads into the slots (the one step that writes shared
-// state in place), restarts the append counters at the entries placed (the
-// log_ctr allocation stays: k_b_begin reads it; its line of lost / refused
-// counts is left alone), swaps log / log_cap and frees the old log;
-// eng_relog_abort drops a placed plan instead.
-// ---------------------------------------------------------------------------
-void eng_relog_abort(Engine* c, RelogPlan* p) {
-  if (!p) return;
-  if (c && (p->log || p->map || p->ctr)) (void)hipSetDevice(c->cfg.device);
-  if (p->log) (void)hipFree(p->log);
-  if (p->map) (void)hipFree(p->map);
-  if (p->ctr) (void)hipFree(p->ctr);
-  *p = RelogPlan{};
-}
-
-int eng_relog_check(Engine* c, uint64_t history_entries) {
-  if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
-  if (!history_entries || !log_entries_fit(history_entries, LOG_PARTS, LOG_PART_MAX))
-    return set_err(c, RL_E_INVALID, "gpu: rl_resize_history: history_entries must be in [1, 2^31]");
-  return RL_OK;
-}
-
-int eng_relog_place(Engine* c, uint64_t history_entries, RelogPlan* p) {
-  if (!p) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  *p = RelogPlan{};
-  if (const int rc = eng_relog_check(c, history_entries)) return rc;
-  RQ_SETTLE(c);
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream;
-  HIPCHK(c, after_batches(c, st));
-  const uint32_t cap = (uint32_t)log_part_cap(history_entries, c->cfg.max_batch, LOG_PARTS, LOG_PART_MAX);
-  std::vector<unsigned long long> old;
-  HIPCHK(c, log_ctr_get(c, old, nullptr));
-  hipError_t e = dalloc(&p->log, (size_t)LOG_PARTS * cap);
-  if (e == hipSuccess) e = dalloc(&p->map, c->nslots);
-  if (e == hipSuccess) e = dalloc(&p->ctr, RELOG_CTR_WORDS);
-  // (the new log is not cleared: entries are written before any chain points at them, as at rl_create)
-  if (e == hipSuccess) e = hipMemsetAsync(p->ctr, 0, RELOG_CTR_WORDS * 8, st);
-  std::vector<unsigned long long> h(RELOG_CTR_WORDS);
-  if (e == hipSuccess) {
-    launch_relog_place(table_view(c), c->nslots, p->log, cap, p->map, p->ctr, st);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h.data(), p->ctr, h.size() * 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();  // (an allocation that failed is this call's error, not the next one's)
-    eng_relog_abort(c, p);
-    return set_err(c, RL_E_HIP, std::string("gpu: rl_resize_history: ") + hipGetErrorString(e) +
-                                    " (the old log, the new log and 4 bytes per slot coexist during the call)");
-  }
-  const unsigned long long* stats = h.data() + RELOG_CTR_STATS;
-  uint64_t fill_max = 0;
-  p->fill.resize(LOG_PARTS);
-  for (uint32_t k = 0; k < LOG_PARTS; k++) {
-    p->fill[k] = h[(size_t)k * LOG_CTR_STRIDE];
-    fill_max = std::max<uint64_t>(fill_max, p->fill[k]);
-  }
-  if (stats[4] || fill_max > cap) {
-    eng_relog_abort(c, p);
-    return set_err(c, RL_E_CAPACITY, "gpu: rl_resize_history: a partition of the new log was asked for " +
-                                         std::to_string(fill_max) + " entries and holds " + std::to_string(cap) +
-                                         " (history_entries of at least " + std::to_string(fill_max * LOG_PARTS) +
-                                         " would fit)");
-  }
-  p->log_cap = cap;
-  p->info.entries_before = (uint64_t)LOG_PARTS * c->log_cap;
-  p->info.entries_after = (uint64_t)LOG_PARTS * cap;
-  for (unsigned long long k : old) {
-    p->appended += k;
-    p->info.written_before += std::min<uint64_t>(k, c->log_cap);
-  }
-  p->info.entries_kept = stats[1];
-  p->info.entries_dropped = p->info.written_before - stats[1];
-  p->info.chains = stats[0];
-  p->info.chains_lost = stats[2];
-  p->info.longest_chain = (uint32_t)stats[3];
-  p->info.fill_max = fill_max;
-  return RL_OK;
-}
-
-int eng_relog_commit(Engine* c, RelogPlan* p) {
-  if (!c || !p || !p->log) return set_err(c, RL_E_INVALID, "gpu: rl_resize_history: nothing placed");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream;
-  std::vector<unsigned long long> hc((size_t)LOG_PARTS * LOG_CTR_STRIDE, 0ull);
-  uint64_t placed = 0;
-  for (uint32_t k = 0; k < LOG_PARTS; k++) {
-    hc[(size_t)k * LOG_CTR_STRIDE] = p->fill[k];
-    placed += p->fill[k];
-  }
-  launch_relog_commit(c->slots, c->nslots, p->map, st);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(c->log_ctr, hc.data(), hc.size() * 8, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {  // (a failed kernel: the device's state is lost either way)
-    eng_relog_abort(c, p);
-    return set_err(c, RL_E_HIP, std::string("gpu: rl_resize_history: commit: ") + hipGetErrorString(e));
-  }
-  c->hist_base += p->appended - placed;  // (history_appended stays where it was)
-  std::swap(c->log, p->log);  // (the plan now holds the old log: freed below)
-  c->log_cap = p->log_cap;
-  c->cfg.history_entries = (uint64_t)LOG_PARTS * p->log_cap;
-  const rl_history_resize_info info = p->info;
-  eng_relog_abort(c, p);
-  p->info = info;
-  return RL_OK;
-}
-
-int eng_resize_history(Engine* c, uint64_t history_entries, rl_history_resize_info* info) {
-  RelogPlan p;
-  if (const int rc = eng_relog_place(c, history_entries, &p)) return rc;
-  if (const int rc = eng_relog_commit(c, &p)) return rc;
-  if (info) *info = p.info;
-  return RL_OK;
-}
-
-// ---------------------------------------------------------------------------
-// rl_resize_arena on one engine: a new pair of arenas (the live one and the
-// sweep's compaction target), the used bytes copied device to device. Offsets
-// are kept, so no slot changes; the cursor (counters[4]) stays.
-// ---------------------------------------------------------------------------
-void eng_arena_abort(Engine* c, ArenaPlan* p) {
-  if (!p) return;
-  if (c && (p->arena || p->arena2)) (void)hipSetDevice(c->cfg.device);
-  if (p->arena) (void)hipFree(p->arena);
-  if (p->arena2) (void)hipFree(p->arena2);
-  *p = ArenaPlan{};
-}
-
-int eng_arena_check(Engine* c, uint64_t arena_bytes) {
-  if (!c) return set_err(c, RL_E_INVALID, "gpu: null ctx");
-  if (!arena_bytes || (arena_bytes & 15u) || arena_bytes / 16 > (1ull << 32))
-    return set_err(c, RL_E_INVALID, "gpu: rl_resize_arena: arena_bytes must be a multiple of 16 in [16, 2^36]");
-  return RL_OK;
-}
-
-int eng_arena_place(Engine* c, uint64_t arena_bytes, ArenaPlan* p) {
-  if (!p) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  *p = ArenaPlan{};
-  if (const int rc = eng_arena_check(c, arena_bytes)) return rc;
-  RQ_SETTLE(c);
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream;
-  HIPCHK(c, after_batches(c, st));
-  unsigned long long used16 = 0;
-  HIPCHK(c, hipMemcpyAsync(&used16, c->s[0].counters + 4, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (used16 > arena_bytes / 16)
-    return set_err(c, RL_E_ARENA_FULL, "gpu: rl_resize_arena: " + std::to_string(used16 * 16) +
-                                           " bytes are in use (rl_sweep compacts the arena)");
-  hipError_t e = dalloc(&p->arena, arena_bytes);
-  if (e == hipSuccess) e = dalloc(&p->arena2, arena_bytes);
-  if (e == hipSuccess && used16) e = hipMemcpyAsync(p->arena, c->arena, used16 * 16, hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    eng_arena_abort(c, p);
-    return set_err(c, RL_E_HIP, std::string("gpu: rl_resize_arena: ") + hipGetErrorString(e) +
-                                    " (the old and the new pair of arenas coexist during the call)");
-  }
-  p->cap16 = arena_bytes / 16;
-  return RL_OK;
-}
-
-void eng_arena_commit(Engine* c, ArenaPlan* p) {
-  std::swap(c->arena, p->arena);  // (the plan now holds the old pair: freed below)
-  std::swap(c->arena2, p->arena2);
-  c->arena_cap16 = p->cap16;
-  c->cfg.arena_bytes = p->cap16 * 16;
-  eng_arena_abort(c, p);
-}
-
-int eng_resize_arena(Engine* c, uint64_t arena_bytes) {
-  ArenaPlan p;
-  if (const int rc = eng_arena_place(c, arena_bytes, &p)) return rc;
-  eng_arena_commit(c, &p);
   return RL_OK;
 }
 
