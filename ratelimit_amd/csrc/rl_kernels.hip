@@ -3030,7 +3030,11 @@ __global__ __launch_bounds__(BkBig::THREADS) void k_bucket_big(
         bucket_segment<B, true>(L, d, nl, base, sk, sh, segsum, rid, run_start, run_end, num_runs, drun);
       }
     } else {
-      if (tid < M.r) run_start[M.rb_heavy + tid] = run_end[M.rb_heavy + tid] = 0;  // hot-key runs left empty
+      if (tid < M.r) {  // hot-key runs left empty; their dup-run entries still name them (k_big_place skipped the
+                        // bucket, and runs_body reads every entry below the dup-run count)
+        run_start[M.rb_heavy + tid] = run_end[M.rb_heavy + tid] = 0;
+        drun[M.db_heavy + tid] = M.rb_heavy + tid;
+      }
       bucket_setup(L, info, ntiles, d);
       BK_STAMP(d, 1);
       if (!bucket_peel(L, d, S, base, ntiles, pt, hin, sk, sv, sh))

@@ -2,7 +2,7 @@
 with the hottest stems of bench.py's C2 batches, under a given stem-hash key.
 
 The stem hash is the library's keyed SipHash-1-3 (rl_device.h StemHasher,
-hash_key_of), restated here for this analysis only; the batches are
+hash_key_of) as tests/bucket_aim.py restates it; the batches are
 bench.py's four distinct C2 batches (rng 0xC2, Zipf(1.1) over 10M tenants).
 
     python tools/bucket_mix.py <hash_seed> [buckets=4]
@@ -15,48 +15,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ratelimit_amd import workloads as W  # noqa: E402
 
-M = (1 << 64) - 1
-
-
-def rotl(x, r):
-    return ((x << r) | (x >> (64 - r))) & M
-
-
-def fmix(k):
-    k ^= k >> 33
-    k = (k * 0xff51afd7ed558ccd) & M
-    k ^= k >> 33
-    k = (k * 0xc4ceb9fe1a85ec53) & M
-    return k ^ (k >> 33)
-
-
-def hash_key(seed):
-    return fmix(seed ^ 0x243F6A8885A308D3), fmix((seed + 0x13198A2E03707344) & M)
-
-
-def stem_hash(key, s):
-    k0, k1 = key
-    v = [k0 ^ 0x736f6d6570736575, k1 ^ 0x646f72616e646f6d, k0 ^ 0x6c7967656e657261, k1 ^ 0x7465646279746573]
-
-    def rnd():
-        v[0] = (v[0] + v[1]) & M; v[1] = rotl(v[1], 13); v[1] ^= v[0]; v[0] = rotl(v[0], 32)
-        v[2] = (v[2] + v[3]) & M; v[3] = rotl(v[3], 16); v[3] ^= v[2]
-        v[0] = (v[0] + v[3]) & M; v[3] = rotl(v[3], 21); v[3] ^= v[0]
-        v[2] = (v[2] + v[1]) & M; v[1] = rotl(v[1], 17); v[1] ^= v[2]; v[2] = rotl(v[2], 32)
-
-    def word(m):
-        v[3] ^= m
-        rnd()
-        v[0] ^= m
-
-    n, i = len(s), 0
-    while i + 8 <= n:
-        word(int.from_bytes(s[i:i + 8], "little"))
-        i += 8
-    word(((n << 56) & M) | (int.from_bytes(s[i:], "little") if i < n else 0))
-    v[2] ^= 0xff
-    rnd(); rnd(); rnd()
-    return (v[0] ^ v[1] ^ v[2] ^ v[3]) or 1
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+from bucket_aim import hash_key, stem_hash  # noqa: E402  (the restated hash, shared with the tests)
 
 
 def main():
