@@ -14,11 +14,11 @@ LIB = os.path.join(HERE, "libratelimit_hip.so")
 # (RL_LOG_TEAR: rl_debug_log_tear, tests/test_gpu_log_tear.py); only
 # rl_kernels.hip differs. The product library has no hook.
 TEAR_LIB = os.path.join(HERE, "libratelimit_hip_tear.so")
-SOURCES = ["rl_kernels.hip", "rl_route.hip", "rl_match.hip", "rl_wire.hip", "rl_resp.hip", "rl_hot.hip", "rl_forget.hip", "rl_scan.hip", "rl_relog.hip", "rl_engine.hip", "rl_maint.hip", "rl_transport.hip",
+SOURCES = ["rl_kernels.hip", "rl_route.hip", "rl_match.hip", "rl_wire.hip", "rl_resp.hip", "rl_hot.hip", "rl_forget.hip", "rl_scan.hip", "rl_relog.hip", "rl_engine.hip", "rl_requests.hip", "rl_maint.hip", "rl_transport.hip",
            "rl_comm.hip",
            "rl_api.hip",
            "rl_pack.cpp"]
-HEADERS = ["rl_device.h", "rl_kernels.h", "rl_tile.h", "rl_slot_img.h", "rl_chain.h", "rl_log_geom.h", "rl_hot_select.h", "rl_forget_match.h", "rl_scan_plan.h", "rl_stem_list.h", "rl_shard_split.h", "rl_match.h", "rl_wire_parse.h", "rl_resp_emit.h", "rl_engine.h", "rl_engine_int.h",
+HEADERS = ["rl_device.h", "rl_kernels.h", "rl_tile.h", "rl_slot_img.h", "rl_chain.h", "rl_log_geom.h", "rl_hot_select.h", "rl_forget_match.h", "rl_scan_plan.h", "rl_stem_list.h", "rl_shard_split.h", "rl_match.h", "rl_wire_parse.h", "rl_resp_emit.h", "rl_engine.h", "rl_engine_int.h", "rl_request_layout.h",
            "rl_comm.h", "rl_transport.h",
            os.path.join("..", "..", "include", "ratelimit_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

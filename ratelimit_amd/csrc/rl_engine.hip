@@ -1,6 +1,7 @@
-// rl_engine.hip — one table shard on one GPU (rl_engine.h): the batch path,
-// the request path, snapshot, sweep and debug; the maintenance calls are
-// rl_maint.hip. Owns the HBM table, the sets of per-batch scratch and the HIP
+// rl_engine.hip — one table shard on one GPU (rl_engine.h): the DoLimit batch
+// path and the host-fed calls, create / destroy, restore, sweep, info, config
+// load, snapshot and debug; the calls that take raw requests are
+// rl_requests.hip, the maintenance calls rl_maint.hip. Owns the HBM table, the sets of per-batch scratch and the HIP
 // streams; every entry point maps the device error words to an rl_status.
 //
 // Batches submitted with eng_do_limit_async(stream = NULL) are pipelined: batch
@@ -29,12 +30,13 @@
 #include "rl_match.h"
 #include "rl_engine.h"
 #include "rl_engine_int.h"
+#include "rl_request_layout.h"
 
 using namespace rl;
 
 static thread_local std::string g_err;
 
-// The helpers rl_maint.hip shares (rl_engine_int.h).
+// The helpers rl_maint.hip and rl_requests.hip share (rl_engine_int.h).
 namespace rl {
 
 int set_err(Engine* c, int code, const std::string& msg) {
@@ -148,10 +150,14 @@ inline double wall_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+}  // namespace
+
+namespace rl {
+
 // Read (and clear) the sticky device error words; synchronises the stream,
 // which must already be ordered after all submitted work.
 // The soft word (descriptor errors answered by statuses) is cleared, not reported.
-int collect(Engine* c, hipStream_t st = nullptr) {
+int collect(Engine* c, hipStream_t st) {
   if (!st) st = c->stream;
   HIPCHK(c, hipMemcpyAsync(c->h_err, c->errw, ERRW_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
@@ -259,6 +265,63 @@ uint32_t enqueue(Engine* c, const BatchDev& b_in, const OutDev& o, int restore, 
   return k;
 }
 
+BatchDev dev_view(const Engine* c, const rl_batch* in, uint32_t stem_cap) {
+  BatchDev b{};
+  b.hk = c->hk;
+  b.n = in->n;
+  b.n_req = in->n_requests;
+  b.n_rules = in->n_rules;
+  b.stem_cap = stem_cap;
+  b.stem_total = stem_cap;  // refined on the device from off[n]
+  b.now_desc = 0;
+  b.stem = in->stem_bytes;
+  b.off = in->stem_off;
+  b.now = in->now;
+  b.req = in->req_idx;
+  b.unit = in->unit;
+  b.flags = in->flags;
+  b.limit = in->limit;
+  b.hits = in->hits;
+  b.rule = in->rule_id;
+  return b;
+}
+
+// A device buffer that grows to the largest size seen (pad: slack past it):
+// freed and allocated anew, so the caller has waited for whatever still reads it.
+int grow(Engine* c, uint8_t** p, size_t* cap, size_t need, size_t pad) {
+  if (need <= *cap) return RL_OK;
+  if (*p) HIPCHK(c, hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  HIPCHK(c, hipMalloc((void**)p, need + pad));
+  *cap = need;
+  return RL_OK;
+}
+
+// The rl_batch over staged device arrays (the sizes are the caller's).
+rl_batch staged_batch(uint32_t n, uint32_t n_requests, uint32_t n_rules, const uint8_t* stem, const uint32_t* off,
+                      const int64_t* now, const uint32_t* req, const uint8_t* unit, const uint8_t* flags,
+                      const uint32_t* limit, const uint32_t* hits, const uint32_t* rule) {
+  rl_batch d{};
+  d.n = n;
+  d.n_requests = n_requests;
+  d.n_rules = n_rules;
+  d.stem_bytes = stem;
+  d.stem_off = off;
+  d.now = now;
+  d.req_idx = req;
+  d.unit = unit;
+  d.flags = flags;
+  d.limit = limit;
+  d.hits = hits;
+  d.rule_id = rule;
+  return d;
+}
+
+}  // namespace rl
+
+namespace {
+
 // A batch submitted through a batch entry point is complete once the work now
 // on `st` is (its outputs written; host-fed: copied back). Keeps at most
 // PROGRESS_RING batches tracked: a caller that runs further ahead waits here
@@ -281,27 +344,6 @@ int check_sizes(Engine* c, const rl_batch* in, uint64_t stem_bytes) {
     return set_err(c, RL_E_CAPACITY, "gpu: batch exceeds configured max_batch/max_requests/max_rules/max_stem_bytes");
   if (in->n && in->n_requests == 0) return set_err(c, RL_E_INVALID, "gpu: descriptors without requests");
   return RL_OK;
-}
-
-BatchDev dev_view(const Engine* c, const rl_batch* in, uint32_t stem_cap) {
-  BatchDev b{};
-  b.hk = c->hk;
-  b.n = in->n;
-  b.n_req = in->n_requests;
-  b.n_rules = in->n_rules;
-  b.stem_cap = stem_cap;
-  b.stem_total = stem_cap;  // refined on the device from off[n]
-  b.now_desc = 0;
-  b.stem = in->stem_bytes;
-  b.off = in->stem_off;
-  b.now = in->now;
-  b.req = in->req_idx;
-  b.unit = in->unit;
-  b.flags = in->flags;
-  b.limit = in->limit;
-  b.hits = in->hits;
-  b.rule = in->rule_id;
-  return b;
 }
 
 // Per-batch scratch of one pipeline buffer (sized for max_batch descriptors).
@@ -366,16 +408,8 @@ int stage(Engine* c, const rl_batch* in, BatchDev* out) {
     HIPCHK(c, hipMemcpyAsync(c->d_hits, in->hits, n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->d_rule, in->rule_id, n * 4, hipMemcpyHostToDevice, st));
   }
-  rl_batch d = *in;
-  d.stem_bytes = c->d_stem;
-  d.stem_off = c->d_off;
-  d.now = c->d_now;
-  d.req_idx = c->d_req;
-  d.unit = c->d_unit;
-  d.flags = c->d_flags;
-  d.limit = c->d_limit;
-  d.hits = c->d_hits;
-  d.rule_id = c->d_rule;
+  const rl_batch d = staged_batch(in->n, in->n_requests, in->n_rules, c->d_stem, c->d_off, c->d_now, c->d_req, c->d_unit,
+                                  c->d_flags, c->d_limit, c->d_hits, c->d_rule);
   *out = dev_view(c, &d, c->cfg.max_stem_bytes);
   return RL_OK;
 }
@@ -546,9 +580,6 @@ void free_host_slots(Engine* c) {
 }
 
 void copy_time_fold(Engine* c, bool all);
-namespace {
-void free_request_slots(Engine* c);
-}
 
 void eng_destroy(Engine* c) {
   if (!c) return;
@@ -994,20 +1025,14 @@ int host_slot_run(Engine* c, HostSlot& h, const rl_batch& d, uint64_t nb, rl_res
   const double w1 = c->host_time ? wall_s() : 0;
   // (stores by a kernel into page-locked outputs: not queued behind the next
   // batch's input copy on the DMA engine, rl_kernels.h ToHost)
-  ToHost th{};
-  auto add = [&](void* dst, const void* src, uint64_t bytes) {
-    th.dst[th.n] = (uint8_t*)dst;
-    th.src[th.n] = (const uint8_t*)src;
-    th.bytes[th.n++] = bytes;
-  };
-  if (n) {
-    add(out->code, h.code, n);
-    add(out->limit_remaining, h.rem, n * 4ull);
-    if (out->reset_s) add(out->reset_s, h.reset, n * 4ull);
-    if (out->status) add(out->status, h.status, n);
-  }
-  if (d.n_rules && out->stats) add(out->stats, h.stats, (size_t)d.n_rules * RL_NUM_STATS * 8);
-  if (th.n) HIPCHK(c, copy_to_host(th, down));
+  ToHostList th(down);
+  th(out->code, h.code, n);
+  th(out->limit_remaining, h.rem, n * 4ull);
+  th(out->reset_s, h.reset, n * 4ull);
+  th(out->status, h.status, n);
+  if (d.n_rules) th(out->stats, h.stats, (size_t)d.n_rules * RL_NUM_STATS * 8);
+  th.flush();
+  HIPCHK(c, th.e);
   HIPCHK(c, hipEventRecord(h.out_done, down));
   const double w2 = c->host_time ? wall_s() : 0;
   HIPCHK(c, track(c, down));
@@ -1051,16 +1076,9 @@ int eng_do_limit_host_async(Engine* c, const rl_batch* in, rl_result* out) {
     HIPCHK(c, hipMemcpyAsync(h.rule, in->rule_id, n * 4ull, hipMemcpyHostToDevice, up));
   }
   HIPCHK(c, hipEventRecord(h.in_done, up));
-  rl_batch d = *in;
-  d.stem_bytes = h.stem;
-  d.stem_off = h.off;
-  d.now = h.now;
-  d.req_idx = h.req;
-  d.unit = h.unit;
-  d.flags = h.flags;
-  d.limit = h.limit;
-  d.hits = h.hits;
-  d.rule_id = h.rule;
+  // (n, n_requests and n_rules are the caller's)
+  const rl_batch d =
+      staged_batch(n, nq, in->n_rules, h.stem, h.off, h.now, h.req, h.unit, h.flags, h.limit, h.hits, h.rule);
   return host_slot_run(c, h, d, nb, out);
 }
 
@@ -1079,14 +1097,27 @@ int eng_compact_check(Engine* c, const rl_batch_compact* in, const rl_result* ou
     return set_err(c, RL_E_CAPACITY, "gpu: batch exceeds configured max_batch/max_requests/max_rules (or > 65536 limits)");
   if (n && !nq) return set_err(c, RL_E_INVALID, "gpu: descriptors without requests");
   const uint64_t B = in->buf_bytes;
-  auto sect = [&](uint64_t off, uint64_t bytes) { return off % 4 == 0 && off <= B && bytes <= B - off; };
-  if (!sect(in->stem_off, (n + 1) * 4ull) || !sect(in->limit_idx, n * 2ull) || !sect(in->req_first, (nq + 1) * 4ull) ||
-      !sect(in->now, nq * 4ull) || !sect(in->hits, nq * 4ull) || !sect(in->limits, in->n_limits * 12ull) ||
-      !sect(in->stem_bytes, 0))
+  using rlreq::in_buf;
+  if (!in_buf(B, in->stem_off, (n + 1) * 4ull) || !in_buf(B, in->limit_idx, n * 2ull) ||
+      !in_buf(B, in->req_first, (nq + 1) * 4ull) || !in_buf(B, in->now, nq * 4ull) || !in_buf(B, in->hits, nq * 4ull) ||
+      !in_buf(B, in->limits, in->n_limits * 12ull) || !in_buf(B, in->stem_bytes, 0))
     return set_err(c, RL_E_INVALID, "gpu: compact batch section outside buf or not 4-byte aligned");
   const uint64_t nb = n ? reinterpret_cast<const uint32_t*>(in->buf + in->stem_off)[n] : 0;
   if (nb > g.max_stem_bytes) return set_err(c, RL_E_CAPACITY, "gpu: batch exceeds configured max_stem_bytes");
-  if (!sect(in->stem_bytes, nb)) return set_err(c, RL_E_INVALID, "gpu: compact batch stems outside buf");
+  if (!in_buf(B, in->stem_bytes, nb)) return set_err(c, RL_E_INVALID, "gpu: compact batch stems outside buf");
+  return RL_OK;
+}
+
+// The next host-fed slot (the slots made on first use), its cbuf first grown to B bytes (the largest buffer
+// seen; behind the slot's previous batch: out_done). The growth comes before
+// the advance: a failed allocation leaves the ring where it was.
+RL_INTERNAL int host_slot_take(Engine* c, uint64_t B, HostSlot** slot) {
+  if (const int rc = ensure_host_slots(c)) return rc;
+  HostSlot& h = c->hs[c->hnext];
+  if (B > h.cbuf_cap) HIPCHK(c, hipEventSynchronize(h.out_done));
+  if (const int rc = grow(c, &h.cbuf, &h.cbuf_cap, B, 64)) return rc;
+  c->hnext = (c->hnext + 1) % NBUF;
+  *slot = &h;
   return RL_OK;
 }
 
@@ -1099,19 +1130,9 @@ int eng_do_limit_compact_async(Engine* c, const rl_batch_compact* in, rl_result*
   const uint64_t B = in->buf_bytes;
   const uint64_t nb = n ? reinterpret_cast<const uint32_t*>(in->buf + in->stem_off)[n] : 0;
   HIPCHK(c, hipSetDevice(g.device));
-  rc = ensure_host_slots(c);
-  if (rc) return rc;
-  const uint32_t j = c->hnext;
-  HostSlot& h = c->hs[j];
-  if (B > h.cbuf_cap) {  // grows to the largest buffer seen (the slot's previous batch drained first)
-    HIPCHK(c, hipEventSynchronize(h.out_done));
-    if (h.cbuf) HIPCHK(c, hipFree(h.cbuf));
-    h.cbuf = nullptr;
-    h.cbuf_cap = 0;
-    HIPCHK(c, dalloc(&h.cbuf, B + 64));
-    h.cbuf_cap = B;
-  }
-  c->hnext = (j + 1) % NBUF;
+  HostSlot* slot = nullptr;
+  if ((rc = host_slot_take(c, B, &slot))) return rc;
+  HostSlot& h = *slot;
   hipStream_t up = hostfed_stream(c, true);
   HIPCHK(c, slot_drained(c, h, up));  // the slot's previous batch is drained
   if (B) HIPCHK(c, hipMemcpyAsync(h.cbuf, in->buf, B, hipMemcpyHostToDevice, up));
@@ -1122,19 +1143,9 @@ int eng_do_limit_compact_async(Engine* c, const rl_batch_compact* in, rl_result*
   HIPCHK(c, hipStreamWaitEvent(c->pipe[c->next], h.in_done, 0));
   launch_unpack(*in, h.cbuf, h.req, h.unit, h.flags, h.limit, h.hits, h.rule, h.now, c->s[c->next].err,
                 c->pipe[c->next]);
-  rl_batch d{};
-  d.n = n;
-  d.n_requests = nq;
-  d.n_rules = in->n_rules;
-  d.stem_bytes = h.cbuf + in->stem_bytes;
-  d.stem_off = reinterpret_cast<const uint32_t*>(h.cbuf + in->stem_off);
-  d.now = h.now;
-  d.req_idx = h.req;
-  d.unit = h.unit;
-  d.flags = h.flags;
-  d.limit = h.limit;
-  d.hits = h.hits;
-  d.rule_id = h.rule;
+  const rl_batch d = staged_batch(n, nq, in->n_rules, h.cbuf + in->stem_bytes,
+                                  reinterpret_cast<const uint32_t*>(h.cbuf + in->stem_off), h.now, h.req, h.unit,
+                                  h.flags, h.limit, h.hits, h.rule);
   return host_slot_run(c, h, d, nb, out);
 }
 
@@ -1151,20 +1162,21 @@ int eng_prefixed_check(Engine* c, const rl_batch_prefixed* in, const rl_result* 
   if (n > g.max_batch || nq > g.max_requests || in->n_rules > g.max_rules || in->n_limits > 65536)
     return set_err(c, RL_E_CAPACITY, "gpu: batch exceeds configured max_batch/max_requests/max_rules (or > 65536 limits)");
   if (n && !nq) return set_err(c, RL_E_INVALID, "gpu: descriptors without requests");
-  const uint32_t T = (nq + RL_PREFIXED_TILE - 1) / RL_PREFIXED_TILE;
+  const uint32_t T = rlreq::tiles(nq, RL_PREFIXED_TILE);
   *tiles = T;
   const uint64_t B = in->buf_bytes;
-  auto sect = [&](uint64_t off, uint64_t bytes) { return off % 4 == 0 && off <= B && bytes <= B - off; };
+  using rlreq::in_buf;
   if (!in->buf && B) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  if (!sect(in->index, 16ull * (T + 1)) || !sect(in->req, nq * 4ull) || !sect(in->now, nq * 4ull) ||
-      !sect(in->hits, nq * 4ull) || !sect(in->desc, n * 4ull) || !sect(in->limits, in->n_limits * 12ull))
+  if (!in_buf(B, in->index, 16ull * (T + 1)) || !in_buf(B, in->req, nq * 4ull) || !in_buf(B, in->now, nq * 4ull) ||
+      !in_buf(B, in->hits, nq * 4ull) || !in_buf(B, in->desc, n * 4ull) ||
+      !in_buf(B, in->limits, in->n_limits * 12ull))
     return set_err(c, RL_E_INVALID, "gpu: prefixed batch section outside buf or not 4-byte aligned");
   const uint32_t* ix = reinterpret_cast<const uint32_t*>(in->buf + in->index);
   const uint32_t* tot = ix + 4ull * T;
-  if (ix[0] || ix[1] || ix[2] || ix[3] || tot[0] != n)
+  if (!rlreq::index_ends_ok(ix, T, n))
     return set_err(c, RL_E_INVALID, "gpu: prefixed batch index does not start at zero or end at n");
   if (tot[3] > g.max_stem_bytes) return set_err(c, RL_E_CAPACITY, "gpu: batch exceeds configured max_stem_bytes");
-  if (!sect(in->prefix_bytes, tot[1]) || !sect(in->suffix_bytes, tot[2]))
+  if (!in_buf(B, in->prefix_bytes, tot[1]) || !in_buf(B, in->suffix_bytes, tot[2]))
     return set_err(c, RL_E_INVALID, "gpu: prefixed batch prefix or suffix bytes outside buf");
   return RL_OK;
 }
@@ -1181,19 +1193,9 @@ int eng_do_limit_prefixed_async(Engine* c, const rl_batch_prefixed* in, rl_resul
   const uint64_t B = in->buf_bytes;
   const uint64_t nb = reinterpret_cast<const uint32_t*>(in->buf + in->index)[4ull * T + 3];
   HIPCHK(c, hipSetDevice(g.device));
-  rc = ensure_host_slots(c);
-  if (rc) return rc;
-  const uint32_t j = c->hnext;
-  HostSlot& h = c->hs[j];
-  if (B > h.cbuf_cap) {  // grows to the largest buffer seen (the slot's previous batch drained first)
-    HIPCHK(c, hipEventSynchronize(h.out_done));
-    if (h.cbuf) HIPCHK(c, hipFree(h.cbuf));
-    h.cbuf = nullptr;
-    h.cbuf_cap = 0;
-    HIPCHK(c, dalloc(&h.cbuf, B + 64));
-    h.cbuf_cap = B;
-  }
-  c->hnext = (j + 1) % NBUF;
+  HostSlot* slot = nullptr;
+  if ((rc = host_slot_take(c, B, &slot))) return rc;
+  HostSlot& h = *slot;
   hipStream_t up = hostfed_stream(c, true);
   const double w1 = c->host_time ? wall_s() : 0;
   if (c->copy_time) HIPCHK(c, hipEventRecord(c->ct_ev[2][c->ct_n % 64], up));
@@ -1216,19 +1218,8 @@ int eng_do_limit_prefixed_async(Engine* c, const rl_batch_prefixed* in, rl_resul
     c->ht[2] += w3 - w2;
     c->ht_n++;
   }
-  rl_batch d{};
-  d.n = n;
-  d.n_requests = nq;
-  d.n_rules = in->n_rules;
-  d.stem_bytes = h.stem;
-  d.stem_off = h.off;
-  d.now = h.now;
-  d.req_idx = h.req;
-  d.unit = h.unit;
-  d.flags = h.flags;
-  d.limit = h.limit;
-  d.hits = h.hits;
-  d.rule_id = h.rule;
+  const rl_batch d =
+      staged_batch(n, nq, in->n_rules, h.stem, h.off, h.now, h.req, h.unit, h.flags, h.limit, h.hits, h.rule);
   return host_slot_run(c, h, d, nb, out);
 }
 
@@ -1590,1126 +1581,6 @@ int eng_config_load(Engine* c, const rl_config_tree* t) {
   d.key_word = (uint32_t)(key_off / 4);
   c->cfg_dev = d;
   c->cfg_loaded = true;
-  return RL_OK;
-}
-
-namespace {
-// A finished verdict block (device, verdict_layout(nq)) -> the caller's arrays.
-hipError_t verdict_d2h(const uint8_t* block, uint32_t nq, rl_request_verdict* v, hipStream_t st) {
-  const VerdictLayout L = verdict_layout(nq);
-  hipError_t e = hipSuccess;
-  auto get = [&](void* dst, size_t off, size_t bytes) {
-    if (e == hipSuccess && dst && bytes) e = hipMemcpyAsync(dst, block + off, bytes, hipMemcpyDeviceToHost, st);
-  };
-  get(v->overall_code, L.o_code, nq);
-  get(v->flags, L.o_flags, nq);
-  get(v->min_descriptor, L.o_min, nq * 4ull);
-  get(v->header_limit, L.o_limit, nq * 4ull);
-  get(v->header_remaining, L.o_rem, nq * 4ull);
-  get(v->header_reset_s, L.o_reset, nq * 4ull);
-  get(v->global_shadow, L.shadow, 8);
-  return e;
-}
-}  // namespace
-
-int eng_do_limit_requests(Engine* c, const rl_request_batch* in, rl_request_result* out, RequestsDoLimit run,
-                          void* user, uint32_t opts, rl_request_verdict* verdict) {
-  if (!c || !in || (!out && !verdict)) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  RQ_SETTLE(c);
-  if (verdict && in->n_requests && !verdict->overall_code)
-    return set_err(c, RL_E_INVALID, "gpu: rl_request_verdict without overall_code");
-  if (verdict && (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW)) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
-  // checkServiceErr(snappedConfig != nil, ...) (ratelimit.go:106)
-  if (!c->cfg_loaded) return set_err(c, RL_E_INVALID, "gpu: no rate limit configuration loaded");
-  const uint32_t n = in->n_descriptors, nq = in->n_requests, ne = in->n_entries;
-  if (n > c->cfg.max_batch || nq > c->cfg.max_requests || in->n_rules > c->cfg.max_rules)
-    return set_err(c, RL_E_CAPACITY, "gpu: request batch exceeds configured max_batch/max_requests/max_rules");
-  if (n && !nq) return set_err(c, RL_E_INVALID, "gpu: descriptors without requests");
-  if (!in->domain_off || !in->entry_first || !in->desc_off || (nq && (!in->now || !in->hits)) ||
-      (n && !in->req_idx) || (ne && (!in->key_len || !in->value_len)))
-    return set_err(c, RL_E_INVALID, "gpu: null request batch array");
-  const bool ovr = in->override_flags != nullptr;
-  if (ovr && (!in->override_rpu || !in->override_unit || !in->override_rule))
-    return set_err(c, RL_E_INVALID, "gpu: override_flags without override_rpu/unit/rule");
-  if (in->entry_first[0] != 0 || in->entry_first[n] != ne || in->desc_off[0] != 0 || in->domain_off[0] != 0)
-    return set_err(c, RL_E_INVALID, "gpu: request batch offsets must start at 0 and end at n_entries");
-  const uint64_t dom_bytes = in->domain_off[nq], desc_bytes = in->desc_off[n];
-  if ((dom_bytes && !in->domain_bytes) || (desc_bytes && !in->desc_bytes))
-    return set_err(c, RL_E_INVALID, "gpu: null request byte array");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  // one device buffer, carved (256-B aligned pieces)
-  const size_t scan = n ? match_scan_bytes(n) : 0;
-  size_t need = 0;
-  auto piece = [&need](size_t bytes) {
-    const size_t o = need;
-    need += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_dom = piece(dom_bytes), o_domoff = piece((nq + 1) * 4ull), o_hits = piece(nq * 4ull),
-               o_req = piece(n * 4ull), o_ent = piece((n + 1) * 4ull), o_doff = piece((n + 1) * 4ull),
-               o_desc = piece(desc_bytes), o_kl = piece(ne * 2ull), o_vl = piece(ne * 2ull),
-               o_ovf = piece(ovr ? n : 0), o_ovr = piece(ovr ? n * 4ull : 0), o_ovu = piece(ovr ? n : 0),
-               o_ovrule = piece(ovr ? n * 4ull : 0), o_v = piece(n * 16ull), o_kind = piece(n * 4ull),
-               o_rpu = piece(n * 4ull), o_rule = piece(n * 4ull), o_cnt = piece(16), o_code = piece(n),
-               o_rem = piece(n * 4ull), o_reset = piece(n * 4ull), o_match = piece(n), o_orule = piece(n * 4ull),
-               o_orpu = piece(n * 4ull), o_ounit = piece(n), o_tmp = piece(scan);
-  const VerdictLayout vl = verdict_layout(nq);
-  const size_t o_verdict = verdict ? piece(vl.bytes) : 0;
-  hipStream_t st = c->stream;
-  HIPCHK(c, after_batches(c, st));
-  if (need > c->mbuf_cap) {
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (c->mbuf) (void)hipFree(c->mbuf);
-    c->mbuf = nullptr;
-    c->mbuf_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&c->mbuf, need));
-    c->mbuf_cap = need;
-  }
-  uint8_t* B = c->mbuf;
-  auto h2d = [&](size_t off, const void* src, size_t bytes) {
-    return bytes ? hipMemcpyAsync(B + off, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-  };
-  HIPCHK(c, h2d(o_dom, in->domain_bytes, dom_bytes));
-  HIPCHK(c, h2d(o_domoff, in->domain_off, (nq + 1) * 4ull));
-  HIPCHK(c, h2d(o_hits, in->hits, nq * 4ull));
-  HIPCHK(c, h2d(o_req, in->req_idx, n * 4ull));
-  HIPCHK(c, h2d(o_ent, in->entry_first, (n + 1) * 4ull));
-  HIPCHK(c, h2d(o_doff, in->desc_off, (n + 1) * 4ull));
-  HIPCHK(c, h2d(o_desc, in->desc_bytes, desc_bytes));
-  HIPCHK(c, h2d(o_kl, in->key_len, ne * 2ull));
-  HIPCHK(c, h2d(o_vl, in->value_len, ne * 2ull));
-  if (ovr) {
-    HIPCHK(c, h2d(o_ovf, in->override_flags, n));
-    HIPCHK(c, h2d(o_ovr, in->override_rpu, n * 4ull));
-    HIPCHK(c, h2d(o_ovu, in->override_unit, n));
-    HIPCHK(c, h2d(o_ovrule, in->override_rule, n * 4ull));
-  }
-  if (nq) HIPCHK(c, hipMemcpyAsync(c->d_now, in->now, nq * 8ull, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemsetAsync(B + o_cnt, 0, 16, st));
-  ReqDev r;
-  r.n_req = nq;
-  r.n_desc = n;
-  r.n_ent = ne;
-  r.dom_total = (uint32_t)dom_bytes;
-  r.desc_total = (uint32_t)desc_bytes;
-  r.dom = B + o_dom;
-  r.dom_off = (const uint32_t*)(B + o_domoff);
-  r.hits = (const uint32_t*)(B + o_hits);
-  r.req = (const uint32_t*)(B + o_req);
-  r.ent_first = (const uint32_t*)(B + o_ent);
-  r.desc_off = (const uint32_t*)(B + o_doff);
-  r.desc = B + o_desc;
-  r.klen = (const uint16_t*)(B + o_kl);
-  r.vlen = (const uint16_t*)(B + o_vl);
-  r.ovf = ovr ? B + o_ovf : nullptr;
-  r.ov_rpu = ovr ? (const uint32_t*)(B + o_ovr) : nullptr;
-  r.ov_unit = ovr ? B + o_ovu : nullptr;
-  r.ov_rule = ovr ? (const uint32_t*)(B + o_ovrule) : nullptr;
-  MatchBuf m{(unsigned long long*)(B + o_v), (uint32_t*)(B + o_kind), (uint32_t*)(B + o_rpu),
-             (uint32_t*)(B + o_rule), (uint32_t*)(B + o_cnt)};
-  // the matched descriptors become an ordinary DoLimit batch in the staging buffers
-  PackOut po{c->d_stem, c->d_off, c->d_req, c->d_unit, c->d_flags, c->d_limit, c->d_hits, c->d_rule,
-             c->cfg.max_stem_bytes};
-  launch_match(c->cfg_dev, r, m, po, B + o_tmp, scan, st);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->h_match, B + o_cnt, 16, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (c->h_match[2] & MATCH_ERR_REQ)
-    return set_err(c, RL_E_INVALID, "gpu: malformed request batch (request index or entry byte layout)");
-  if (c->h_match[2] & MATCH_ERR_CAP)
-    return set_err(c, RL_E_CAPACITY, "gpu: matched stems exceed max_stem_bytes");
-  const uint32_t nm = n ? c->h_match[0] : 0;
-  if (!n) {  // off[0] of the empty batch
-    HIPCHK(c, hipMemsetAsync(c->d_off, 0, 4, st));
-  }
-  rl_batch pb{};
-  pb.n = nm;
-  pb.n_requests = nq;
-  pb.n_rules = in->n_rules;
-  pb.stem_bytes = c->d_stem;
-  pb.stem_off = c->d_off;
-  pb.now = c->d_now;
-  pb.req_idx = c->d_req;
-  pb.unit = c->d_unit;
-  pb.flags = c->d_flags;
-  pb.limit = c->d_limit;
-  pb.hits = c->d_hits;
-  pb.rule_id = c->d_rule;
-  if (run) {
-    rl_result dout{};
-    dout.code = c->d_code;
-    dout.limit_remaining = c->d_rem;
-    dout.reset_s = c->d_reset;
-    dout.stats = reinterpret_cast<uint64_t*>(c->d_stats);
-    const int rc = run(user, &pb, &dout, st);
-    if (rc) return rc;  // (the runner's own error report)
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-  } else {
-    BatchDev b = dev_view(c, &pb, c->cfg.max_stem_bytes);
-    OutDev o{c->d_code, c->d_rem, c->d_reset, c->d_stats, nullptr};
-    enqueue(c, b, o, 0, st, false);
-  }
-  ReqOutDev ro{B + o_code, (uint32_t*)(B + o_rem), (uint32_t*)(B + o_reset), B + o_match,
-               (uint32_t*)(B + o_orule), (uint32_t*)(B + o_orpu), B + o_ounit};
-  launch_match_expand(r, m, c->d_code, c->d_rem, c->d_reset, ro, st);
-  HIPCHK(c, hipGetLastError());
-  if (verdict && nq) {
-    // the verdict reads the expanded answers where they lie
-    const VerdictDev vd = verdict_view(nq, n, opts, r.req, ro.match, ro.code, ro.rem, ro.reset, ro.rpu, B + o_verdict);
-    HIPCHK(c, launch_verdict(vd, B + o_verdict, st));
-  }
-  auto d2h = [&](void* dst, size_t off, size_t bytes) {
-    return (bytes && dst) ? hipMemcpyAsync(dst, B + off, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
-  };
-  if (out) {
-    HIPCHK(c, d2h(out->code, o_code, n));
-    HIPCHK(c, d2h(out->limit_remaining, o_rem, n * 4ull));
-    HIPCHK(c, d2h(out->reset_s, o_reset, n * 4ull));
-    HIPCHK(c, d2h(out->match, o_match, n));
-    HIPCHK(c, d2h(out->rule_id, o_orule, n * 4ull));
-    HIPCHK(c, d2h(out->requests_per_unit, o_orpu, n * 4ull));
-    HIPCHK(c, d2h(out->unit, o_ounit, n));
-    if (in->n_rules && out->stats)
-      HIPCHK(c, hipMemcpyAsync(out->stats, c->d_stats, (size_t)in->n_rules * RL_NUM_STATS * 8, hipMemcpyDeviceToHost, st));
-  }
-  c->batches++;
-  c->decisions += nm;
-  const int rc = collect(c);
-  if (rc || !verdict) return rc;
-  // copied only now that the batch is known good: a failed batch leaves *verdict alone
-  if (nq) {
-    HIPCHK(c, verdict_d2h(B + o_verdict, nq, verdict, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-  } else if (verdict->global_shadow) {
-    *verdict->global_shadow = 0;
-  }
-  return RL_OK;
-}
-
-// ---- packed request batches, pipelined (rl_do_limit_requests_packed_async) --
-
-// The host checks only what the copy and the unpack's bounds rely on: sections
-// inside buf, the index's first entry zero and its last the batch's sizes;
-// every tile's own entry and the override list are checked on the device.
-int eng_requests_packed_check(Engine* c, const rl_request_batch_packed* in, const rl_request_result* out, uint32_t opts,
-                              const rl_request_verdict* verdict, uint32_t* tiles) {
-  if (!c || !in || (!out && !verdict)) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  if (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
-  if (!c->cfg_loaded) return set_err(c, RL_E_INVALID, "gpu: no rate limit configuration loaded");
-  const rl_config& g = c->cfg;
-  const uint32_t n = in->n_descriptors, nq = in->n_requests, ne = in->n_entries;
-  if (n > g.max_batch || nq > g.max_requests || in->n_rules > g.max_rules)
-    return set_err(c, RL_E_CAPACITY, "gpu: request batch exceeds configured max_batch/max_requests/max_rules");
-  if (n && !nq) return set_err(c, RL_E_INVALID, "gpu: descriptors without requests");
-  if (in->reserved) return set_err(c, RL_E_INVALID, "gpu: packed request batch: reserved field not zero");
-  if (in->n_overrides > n) return set_err(c, RL_E_INVALID, "gpu: packed request batch: more overrides than descriptors");
-  const uint32_t T = (nq + RL_REQUESTS_TILE - 1) / RL_REQUESTS_TILE;
-  *tiles = T;
-  const uint64_t B = in->buf_bytes;
-  if (!in->buf) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  auto sect = [&](uint64_t off, uint64_t bytes) { return off % 4 == 0 && off <= B && bytes <= B - off; };
-  if (!sect(in->index, 16ull * (T + 1)) || !sect(in->req, nq * 4ull) || !sect(in->now, nq * 4ull) ||
-      !sect(in->hits, nq * 4ull) || !sect(in->desc, n * 2ull) || !sect(in->key_len, ne * 2ull) ||
-      !sect(in->value_len, ne * 2ull) || !sect(in->overrides, in->n_overrides * (uint64_t)sizeof(rl_request_override)) ||
-      !sect(in->domain_bytes, 0) || !sect(in->entry_bytes, 0))
-    return set_err(c, RL_E_INVALID, "gpu: packed request batch section outside buf or not 4-byte aligned");
-  const uint32_t* ix = reinterpret_cast<const uint32_t*>(in->buf + in->index);
-  const uint32_t* tot = ix + 4ull * T;
-  if (ix[0] || ix[1] || ix[2] || ix[3] || tot[0] != n || tot[1] != ne)
-    return set_err(c, RL_E_INVALID, "gpu: packed request batch index does not start at zero or end at the batch's sizes");
-  if (tot[3] > g.max_stem_bytes) return set_err(c, RL_E_CAPACITY, "gpu: request batch's entry bytes exceed max_stem_bytes");
-  if (!sect(in->domain_bytes, tot[2]) || !sect(in->entry_bytes, tot[3]))
-    return set_err(c, RL_E_INVALID, "gpu: packed request batch domain or entry bytes outside buf");
-  return RL_OK;
-}
-
-namespace {
-
-void free_request_slots(Engine* c) {
-  if (!c->rq) return;
-  for (uint32_t j = 0; j < RL_REQUESTS_INFLIGHT; j++) {
-    RequestSlot& s = c->rq[j];
-    HostSlot& h = s.h;
-    void* bufs[] = {h.stem, h.off, h.req, h.limit, h.hits, h.rule, h.now, h.unit, h.flags, h.code, h.rem,
-                    h.reset, h.stats, h.cbuf, s.mbuf, s.wbuf};
-    for (void* p : bufs)
-      if (p) (void)hipFree(p);
-    if (s.h_cnt) (void)hipHostFree(s.h_cnt);
-    if (s.h_wcnt) (void)hipHostFree(s.h_wcnt);
-    if (s.count_done) (void)hipEventDestroy(s.count_done);
-    if (s.wire_done) (void)hipEventDestroy(s.wire_done);
-    if (h.in_done) (void)hipEventDestroy(h.in_done);
-  }
-  if (c->rq_copy) (void)hipStreamDestroy(c->rq_copy);
-  c->rq_copy = nullptr;
-  delete[] c->rq;
-  c->rq = nullptr;
-  c->rq_head = c->rq_n = 0;
-}
-
-int ensure_request_slots(Engine* c) {
-  if (c->rq) return RL_OK;
-  const rl_config& g = c->cfg;
-  c->rq = new RequestSlot[RL_REQUESTS_INFLIGHT];
-  bool ok = rl_stream_create(&c->rq_copy, SR_HOSTCOPY) == hipSuccess;
-  for (uint32_t j = 0; j < RL_REQUESTS_INFLIGHT; j++) {
-    RequestSlot& s = c->rq[j];
-    HostSlot& h = s.h;
-    s.st = c->pipe[j % NBUF];
-    ok = ok && dalloc(&h.stem, (size_t)g.max_stem_bytes + 64) == hipSuccess &&
-         dalloc(&h.off, (size_t)g.max_batch + 1) == hipSuccess && dalloc(&h.req, g.max_batch) == hipSuccess &&
-         dalloc(&h.limit, g.max_batch) == hipSuccess && dalloc(&h.hits, g.max_batch) == hipSuccess &&
-         dalloc(&h.rule, g.max_batch) == hipSuccess && dalloc(&h.now, g.max_requests) == hipSuccess &&
-         dalloc(&h.unit, g.max_batch) == hipSuccess && dalloc(&h.flags, g.max_batch) == hipSuccess &&
-         dalloc(&h.code, g.max_batch) == hipSuccess && dalloc(&h.rem, g.max_batch) == hipSuccess &&
-         dalloc(&h.reset, g.max_batch) == hipSuccess &&
-         dalloc(&h.stats, (size_t)g.max_rules * RL_NUM_STATS) == hipSuccess &&
-         hipHostMalloc((void**)&s.h_cnt, 16, hipHostMallocDefault) == hipSuccess &&
-         hipEventCreateWithFlags(&s.count_done, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&h.in_done, hipEventDisableTiming) == hipSuccess;
-  }
-  if (!ok) {
-    free_request_slots(c);
-    return set_err(c, RL_E_HIP, "gpu: request slot allocation failed");
-  }
-  return RL_OK;
-}
-
-// Device arrays into the caller's host arrays on `st`, ToHost's capacity at a time.
-struct ToHostList {
-  ToHost th{};
-  hipStream_t st;
-  hipError_t e = hipSuccess;
-  explicit ToHostList(hipStream_t s) : st(s) {}
-  void flush() {
-    if (th.n && e == hipSuccess) e = copy_to_host(th, st);
-    th.n = 0;
-  }
-  void add(void* dst, const void* src, uint64_t bytes) {
-    if (!dst || !bytes) return;
-    if (th.n == TO_HOST_MAX) flush();
-    th.dst[th.n] = (uint8_t*)dst;
-    th.src[th.n] = (const uint8_t*)src;
-    th.bytes[th.n++] = bytes;
-  }
-};
-
-// The serializer's view of one batch: its answers, its verdict block and its staging (resp_layout at `stage`).
-RespDev resp_view(uint32_t nq, uint32_t n, uint64_t bound, const uint32_t* req, const uint32_t* desc_first,
-                  const uint8_t* status, const ReqOutDev& ro, uint8_t* vblock, uint8_t* stage) {
-  const VerdictLayout V = verdict_layout(nq);
-  const RespLayout L = resp_layout(nq, n, bound);
-  RespDev r;
-  r.n_req = nq;
-  r.n_desc = n;
-  r.cap = (uint32_t)L.cap;
-  r.req = req;
-  r.desc_first = desc_first;
-  r.status = status;
-  r.code = ro.code;
-  r.rem = ro.rem;
-  r.reset = ro.reset;
-  r.match = ro.match;
-  r.rpu = ro.rpu;
-  r.unit = ro.unit;
-  r.o_code = vblock + V.o_code;
-  r.o_min = (const uint32_t*)(vblock + V.o_min);
-  r.o_limit = (const uint32_t*)(vblock + V.o_limit);
-  r.o_rem = (const uint32_t*)(vblock + V.o_rem);
-  r.o_reset = (const uint32_t*)(vblock + V.o_reset);
-  r.soff = (uint32_t*)(stage + L.soff);
-  r.resp_off = (uint32_t*)(stage + L.resp_off);
-  r.tmp = stage + L.tmp;
-  r.tmp_bytes = L.tmp_bytes;
-  r.bytes = stage + L.bytes;
-  return r;
-}
-
-// The second half of the batch in slot s, whose count has arrived.
-int request_second_half(Engine* c, RequestSlot& s) {
-  HostSlot& h = s.h;
-  const uint64_t seq = s.seq;
-  if (s.failed) {  // a wire batch its middle stage refused (rq_fail is set): its place in the progress ring only
-    HIPCHK(c, hipEventRecord(c->done_ring[seq % PROGRESS_RING], s.st));
-    return RL_OK;
-  }
-  const uint32_t n = s.n, nq = s.nq, bits = s.h_cnt[2];
-  if (bits) {
-    // failed in the match stage: no second half, the table untouched; its
-    // place in the progress ring completes with the work before it
-    if (!c->rq_fail) {
-      if (bits & MATCH_ERR_WIRE) {
-        c->rq_fail = RL_E_INVALID;
-        c->rq_fail_msg = "gpu: wire batch: a message's second walk left its counted share";
-      } else if (bits & MATCH_ERR_UNPACK) {
-        c->rq_fail = RL_E_INVALID;
-        c->rq_fail_msg = "gpu: malformed packed request batch (tile index or override list)";
-      } else if (bits & MATCH_ERR_REQ) {
-        c->rq_fail = RL_E_INVALID;
-        c->rq_fail_msg = "gpu: malformed request batch (request index or entry byte layout)";
-      } else {
-        c->rq_fail = RL_E_CAPACITY;
-        c->rq_fail_msg = "gpu: matched stems exceed max_stem_bytes";
-      }
-    }
-    HIPCHK(c, hipEventRecord(c->done_ring[seq % PROGRESS_RING], s.st));
-    return RL_OK;
-  }
-  const uint32_t nm = n ? s.h_cnt[0] : 0;
-  hipStream_t a = c->pipe[c->next];  // (the count is on the host: the first half is complete, nothing to wait for)
-  if (!n) HIPCHK(c, hipMemsetAsync(h.off, 0, 4, a));  // off[0] of the empty batch
-  rl_batch pb{};
-  pb.n = nm;
-  pb.n_requests = nq;
-  pb.n_rules = s.n_rules;
-  pb.stem_bytes = h.stem;
-  pb.stem_off = h.off;
-  pb.now = h.now;
-  pb.req_idx = h.req;
-  pb.unit = h.unit;
-  pb.flags = h.flags;
-  pb.limit = h.limit;
-  pb.hits = h.hits;
-  pb.rule_id = h.rule;
-  BatchDev b = dev_view(c, &pb, c->cfg.max_stem_bytes);
-  OutDev o{h.code, h.rem, h.reset, s.n_rules ? h.stats : nullptr, nullptr};
-  const uint32_t k = enqueue(c, b, o, 0, nullptr, true);
-  a = c->pipe[k];
-  s.st = a;
-  launch_match_expand(s.r, s.m, h.code, h.rem, h.reset, s.ro, a);
-  HIPCHK(c, hipGetLastError());
-  if ((s.has_verdict || s.has_resp) && nq) {
-    const VerdictDev vd = verdict_view(nq, n, s.opts, s.r.req, s.ro.match, s.ro.code, s.ro.rem, s.ro.reset, s.ro.rpu,
-                                       s.vblock);
-    HIPCHK(c, launch_verdict(vd, s.vblock, a));
-    if (s.wire) {  // a deferred or malformed request's entry is no answer
-      launch_wire_code(s.w.status, s.vblock + verdict_layout(nq).o_code, nq, a);
-      HIPCHK(c, hipGetLastError());
-    }
-  }
-  ToHostList th(a);
-  if (s.has_resp && nq) {  // the responses: serialized from the answers and the verdict where they lie
-    const RespDev rd = resp_view(nq, n, s.resp_bound, s.r.req, s.w.desc_first, s.w.status, s.ro, s.vblock,
-                                 s.mbuf + s.o_resp);
-    HIPCHK(c, launch_respond(rd, s.fmt, a));
-    launch_respond_to_host(rd, s.resp_dst, a);
-    HIPCHK(c, hipGetLastError());
-    th.add(s.resp.resp_off, rd.resp_off, (nq + 1) * 4ull);
-  }
-  if (s.wire) {
-    th.add(s.wres.req_status, s.w.status, nq);
-    th.add(s.wres.desc_first, s.w.desc_first, (nq + 1) * 4ull);
-    th.add(s.wres.n_descriptors, s.w.cnt, 4);
-  }
-  if (s.has_out) {
-    const rl_request_result& out = s.out;
-    th.add(out.code, s.ro.code, n);
-    th.add(out.limit_remaining, s.ro.rem, n * 4ull);
-    th.add(out.reset_s, s.ro.reset, n * 4ull);
-    th.add(out.match, s.ro.match, n);
-    th.add(out.rule_id, s.ro.rule, n * 4ull);
-    th.add(out.requests_per_unit, s.ro.rpu, n * 4ull);
-    th.add(out.unit, s.ro.unit, n);
-    if (s.n_rules) th.add(out.stats, h.stats, (size_t)s.n_rules * RL_NUM_STATS * 8);
-  }
-  if (s.has_verdict && nq) {
-    const VerdictLayout L = verdict_layout(nq);
-    const rl_request_verdict& v = s.verdict;
-    th.add(v.overall_code, s.vblock + L.o_code, nq);
-    th.add(v.flags, s.vblock + L.o_flags, nq);
-    th.add(v.min_descriptor, s.vblock + L.o_min, nq * 4ull);
-    th.add(v.header_limit, s.vblock + L.o_limit, nq * 4ull);
-    th.add(v.header_remaining, s.vblock + L.o_rem, nq * 4ull);
-    th.add(v.header_reset_s, s.vblock + L.o_reset, nq * 4ull);
-    th.add(v.global_shadow, s.vblock + L.shadow, 8);
-  }
-  th.flush();
-  HIPCHK(c, th.e);
-  HIPCHK(c, hipEventRecord(c->done_ring[seq % PROGRESS_RING], a));
-  HIPCHK(c, hipGetLastError());
-  c->batches++;
-  c->decisions += nm;
-  return RL_OK;
-}
-
-// The middle stage of the wire batch in slot s, whose count words have arrived:
-// the capacity checks, the carve by the now-known sizes, k_wire_emit, the
-// config match and the matched count's way to the host.
-int request_middle(Engine* c, RequestSlot& s) {
-  HostSlot& h = s.h;
-  hipStream_t st = s.st;
-  s.stage = 0;
-  const uint32_t n = s.h_wcnt[0], ne = s.h_wcnt[1], dom_total = s.h_wcnt[2], ent_total = s.h_wcnt[3];
-  const uint32_t bits = s.h_wcnt[4], nq = s.nq;
-  const rl_config& g = c->cfg;
-  int fail = 0;
-  const char* msg = nullptr;
-  if (bits & WIRE_ERR_OFF) {
-    fail = RL_E_INVALID;
-    msg = "gpu: wire batch msg_off decreasing or past msgs_bytes";
-  } else if ((bits & WIRE_ERR_SUM) || n > g.max_batch || (s.has_out && n > s.wres.desc_cap)) {
-    fail = RL_E_CAPACITY;
-    msg = "gpu: wire batch has more descriptors than desc_cap / max_batch";
-  } else if (ent_total > g.max_stem_bytes) {
-    fail = RL_E_CAPACITY;
-    msg = "gpu: request batch's entry bytes exceed max_stem_bytes";
-  }
-  // (the responses' length depends on the counters: the bound stands for it)
-  s.resp_bound = s.has_resp ? rlresp::bound(nq, n, s.fmt) : 0;
-  if (!fail && s.has_resp && (s.resp_bound > s.resp.bytes_cap || s.resp_bound >= (1ull << 32))) {
-    fail = RL_E_CAPACITY;
-    msg = "gpu: wire batch's rl_response_bound exceeds bytes_cap or 32 bits";
-  }
-  if (fail) {
-    if (!c->rq_fail) {
-      c->rq_fail = fail;
-      c->rq_fail_msg = msg;
-    }
-    s.failed = true;
-    HIPCHK(c, hipEventRecord(s.count_done, st));
-    return RL_OK;
-  }
-  const size_t scan = n ? match_scan_bytes(n) : 0;
-  size_t need = 0;
-  auto piece = [&need](size_t bytes) {
-    const size_t o = need;
-    need += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_domoff = piece((nq + 1) * 4ull), o_req = piece(n * 4ull), o_ent = piece((n + 1) * 4ull),
-               o_doff = piece((n + 1) * 4ull), o_hits = piece(nq * 4ull), o_klen = piece(ne * 2ull),
-               o_vlen = piece(ne * 2ull), o_dom = piece(dom_total), o_desc = piece(ent_total), o_v = piece(n * 16ull),
-               o_kind = piece(n * 4ull), o_rpu = piece(n * 4ull), o_rule = piece(n * 4ull), o_cnt = piece(16),
-               o_code = piece(n), o_rem = piece(n * 4ull), o_reset = piece(n * 4ull), o_match = piece(n),
-               o_orule = piece(n * 4ull), o_orpu = piece(n * 4ull), o_ounit = piece(n), o_tmp = piece(scan);
-  // the dense override arrays, as the packed path lays them out: only for a batch that carries overrides
-  const bool has_ov = s.ov && s.h_wcnt[5] && n;
-  const size_t o_ov = has_ov ? piece(n * 10ull) : 0;
-  const bool has_v = s.has_verdict || s.has_resp;
-  const size_t o_verdict = has_v ? piece(verdict_layout(nq).bytes) : 0;
-  s.o_resp = s.has_resp && nq ? piece(resp_layout(nq, n, s.resp_bound).total) : 0;
-  if (need > s.mbuf_cap) {  // (the count words are here: the slot's stream has nothing older in flight)
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (s.mbuf) HIPCHK(c, hipFree(s.mbuf));
-    s.mbuf = nullptr;
-    s.mbuf_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&s.mbuf, need));
-    s.mbuf_cap = need;
-  }
-  uint8_t* M = s.mbuf;
-  HIPCHK(c, hipMemsetAsync(M + o_cnt, 0, 16, st));
-  MatchBuf m{(unsigned long long*)(M + o_v), (uint32_t*)(M + o_kind), (uint32_t*)(M + o_rpu),
-             (uint32_t*)(M + o_rule), (uint32_t*)(M + o_cnt)};
-  WireOut wo;
-  wo.tot = make_uint4(n, ne, dom_total, ent_total);
-  wo.dom_off = (uint32_t*)(M + o_domoff);
-  wo.hits = (uint32_t*)(M + o_hits);
-  wo.now = h.now;
-  wo.req = (uint32_t*)(M + o_req);
-  wo.ent_first = (uint32_t*)(M + o_ent);
-  wo.desc_off = (uint32_t*)(M + o_doff);
-  wo.klen = (uint16_t*)(M + o_klen);
-  wo.vlen = (uint16_t*)(M + o_vlen);
-  wo.dom = M + o_dom;
-  wo.desc = M + o_desc;
-  wo.err = m.count + 2;
-  wo.ov_rpu = has_ov ? (uint32_t*)(M + o_ov) : nullptr;
-  wo.ov_rule = has_ov ? wo.ov_rpu + n : nullptr;
-  wo.ovf = has_ov ? (uint8_t*)(wo.ov_rule + n) : nullptr;
-  wo.ov_unit = has_ov ? wo.ovf + n : nullptr;
-  if (has_ov) HIPCHK(c, hipMemsetAsync(M + o_ov, 0, n * 10ull, st));
-  if (!nq) HIPCHK(c, hipMemsetAsync(wo.dom_off, 0, 4, st));
-  launch_wire_emit(s.w, wo, st, has_ov ? &c->ov : nullptr);
-  ReqDev r;
-  r.n_req = nq;
-  r.n_desc = n;
-  r.n_ent = ne;
-  r.dom_total = dom_total;
-  r.desc_total = ent_total;
-  r.dom = wo.dom;
-  r.dom_off = wo.dom_off;
-  r.hits = wo.hits;
-  r.req = wo.req;
-  r.ent_first = wo.ent_first;
-  r.desc_off = wo.desc_off;
-  r.desc = wo.desc;
-  r.klen = wo.klen;
-  r.vlen = wo.vlen;
-  r.ovf = wo.ovf;
-  r.ov_rpu = wo.ov_rpu;
-  r.ov_unit = wo.ov_unit;
-  r.ov_rule = wo.ov_rule;
-  PackOut po{h.stem, h.off, h.req, h.unit, h.flags, h.limit, h.hits, h.rule, g.max_stem_bytes};
-  launch_match(c->cfg_dev, r, m, po, M + o_tmp, scan, st);
-  HIPCHK(c, hipGetLastError());
-  ToHost th{};
-  th.src[0] = M + o_cnt;
-  th.dst[0] = (uint8_t*)s.h_cnt;
-  th.bytes[0] = 16;
-  th.n = 1;
-  HIPCHK(c, copy_to_host(th, st));
-  HIPCHK(c, hipEventRecord(s.count_done, st));
-  s.n = n;
-  s.r = r;
-  s.m = m;
-  s.ro = ReqOutDev{M + o_code, (uint32_t*)(M + o_rem), (uint32_t*)(M + o_reset), M + o_match,
-                   (uint32_t*)(M + o_orule), (uint32_t*)(M + o_orpu), M + o_ounit};
-  s.vblock = has_v ? M + o_verdict : nullptr;
-  return RL_OK;
-}
-
-}  // namespace
-
-int eng_requests_advance(Engine* c, uint32_t must) {
-  if (!c->rq_n) return RL_OK;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  // wire batches whose count words have arrived: their middle stages, oldest first
-  for (uint32_t i = 0; i < c->rq_n; i++) {
-    RequestSlot& s = c->rq[(c->rq_head + i) % RL_REQUESTS_INFLIGHT];
-    if (s.stage != 1) continue;
-    const hipError_t e = hipEventQuery(s.wire_done);
-    if (e == hipErrorNotReady) break;
-    HIPCHK(c, e);
-    if (const int rc = request_middle(c, s)) return rc;
-  }
-  while (c->rq_n) {
-    RequestSlot& s = c->rq[c->rq_head];
-    if (must) {
-      if (s.stage == 1) {
-        HIPCHK(c, hipEventSynchronize(s.wire_done));
-        if (const int rc = request_middle(c, s)) return rc;
-      }
-      HIPCHK(c, hipEventSynchronize(s.count_done));
-      must--;
-    } else {
-      if (s.stage == 1) break;
-      const hipError_t e = hipEventQuery(s.count_done);
-      if (e == hipErrorNotReady) break;
-      HIPCHK(c, e);
-    }
-    c->rq_head = (c->rq_head + 1) % RL_REQUESTS_INFLIGHT;
-    c->rq_n--;
-    const int rc = request_second_half(c, s);
-    if (rc) return rc;
-  }
-  return RL_OK;
-}
-
-int eng_do_limit_requests_packed_async(Engine* c, const rl_request_batch_packed* in, rl_request_result* out,
-                                       uint32_t opts, rl_request_verdict* verdict) {
-  uint32_t T = 0;
-  int rc = eng_requests_packed_check(c, in, out, opts, verdict, &T);
-  if (rc) return rc;
-  const uint32_t n = in->n_descriptors, nq = in->n_requests, ne = in->n_entries, nov = in->n_overrides;
-  const uint64_t B = in->buf_bytes;
-  const uint32_t* tot = reinterpret_cast<const uint32_t*>(in->buf + in->index) + 4ull * T;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  if ((rc = ensure_request_slots(c))) return rc;
-  // the oldest batches whose count has arrived; a full ring waits for the oldest one's
-  if ((rc = eng_requests_advance(c, c->rq_n == RL_REQUESTS_INFLIGHT ? 1 : 0))) return rc;
-  RequestSlot& s = c->rq[(c->rq_head + c->rq_n) % RL_REQUESTS_INFLIGHT];
-  HostSlot& h = s.h;
-  hipStream_t st = s.st;  // (after the slot's previous batch, in stream order)
-  // the slot's carved buffer (256-B aligned pieces) and its copy of buf grow to the largest batch seen
-  const size_t scan = n ? match_scan_bytes(n) : 0;
-  size_t need = 0;
-  auto piece = [&need](size_t bytes) {
-    const size_t o = need;
-    need += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_domoff = piece((nq + 1) * 4ull), o_req = piece(n * 4ull), o_ent = piece((n + 1) * 4ull),
-               o_doff = piece((n + 1) * 4ull), o_ov = piece(nov ? n * 10ull : 0), o_v = piece(n * 16ull),
-               o_kind = piece(n * 4ull), o_rpu = piece(n * 4ull), o_rule = piece(n * 4ull), o_cnt = piece(16),
-               o_code = piece(n), o_rem = piece(n * 4ull), o_reset = piece(n * 4ull), o_match = piece(n),
-               o_orule = piece(n * 4ull), o_orpu = piece(n * 4ull), o_ounit = piece(n), o_tmp = piece(scan);
-  const size_t o_verdict = verdict ? piece(verdict_layout(nq).bytes) : 0;
-  if (need > s.mbuf_cap || B > h.cbuf_cap) HIPCHK(c, hipStreamSynchronize(st));  // the slot's previous batch
-  if (need > s.mbuf_cap) {
-    if (s.mbuf) HIPCHK(c, hipFree(s.mbuf));
-    s.mbuf = nullptr;
-    s.mbuf_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&s.mbuf, need));
-    s.mbuf_cap = need;
-  }
-  if (B > h.cbuf_cap) {
-    if (h.cbuf) HIPCHK(c, hipFree(h.cbuf));
-    h.cbuf = nullptr;
-    h.cbuf_cap = 0;
-    HIPCHK(c, dalloc(&h.cbuf, B + 64));
-    h.cbuf_cap = B;
-  }
-  // progress: submitted now, complete when its second half is (its ring event is recorded then)
-  if (c->seq_sub - c->seq_done >= PROGRESS_RING) {
-    HIPCHK(c, hipEventSynchronize(c->done_ring[c->seq_done % PROGRESS_RING]));
-    c->seq_done++;
-  }
-  uint8_t* M = s.mbuf;
-  // The copy goes on a stream of its own: the slot's stream still runs its previous batch's second half,
-  // which reads nothing of cbuf (the first half did, and its count has arrived), and the batches' copies
-  // then follow each other on the link without waiting for any kernel.
-  if (B) {
-    HIPCHK(c, hipMemcpyAsync(h.cbuf, in->buf, B, hipMemcpyHostToDevice, c->rq_copy));
-    HIPCHK(c, hipEventRecord(h.in_done, c->rq_copy));
-    HIPCHK(c, hipStreamWaitEvent(st, h.in_done, 0));
-  }
-  HIPCHK(c, hipMemsetAsync(M + o_cnt, 0, 16, st));
-  if (nov) HIPCHK(c, hipMemsetAsync(M + o_ov, 0, n * 10ull, st));
-  // the dense override arrays: rpu and rule (4-byte aligned: n x 4 each), then flags and units
-  uint32_t* ov_rpu = (uint32_t*)(M + o_ov);
-  uint32_t* ov_rule = ov_rpu + n;
-  uint8_t* ovf = (uint8_t*)(ov_rule + n);
-  uint8_t* ov_unit = ovf + n;
-  MatchBuf m{(unsigned long long*)(M + o_v), (uint32_t*)(M + o_kind), (uint32_t*)(M + o_rpu),
-             (uint32_t*)(M + o_rule), (uint32_t*)(M + o_cnt)};
-  launch_unpack_requests(*in, h.cbuf, (uint32_t*)(M + o_domoff), h.now, (uint32_t*)(M + o_req),
-                         (uint32_t*)(M + o_ent), (uint32_t*)(M + o_doff), ovf, ov_rpu, ov_unit, ov_rule, m.count + 2, st);
-  ReqDev r;
-  r.n_req = nq;
-  r.n_desc = n;
-  r.n_ent = ne;
-  r.dom_total = tot[2];
-  r.desc_total = tot[3];
-  r.dom = h.cbuf + in->domain_bytes;
-  r.dom_off = (const uint32_t*)(M + o_domoff);
-  r.hits = (const uint32_t*)(h.cbuf + in->hits);
-  r.req = (const uint32_t*)(M + o_req);
-  r.ent_first = (const uint32_t*)(M + o_ent);
-  r.desc_off = (const uint32_t*)(M + o_doff);
-  r.desc = h.cbuf + in->entry_bytes;
-  r.klen = (const uint16_t*)(h.cbuf + in->key_len);
-  r.vlen = (const uint16_t*)(h.cbuf + in->value_len);
-  r.ovf = nov ? ovf : nullptr;
-  r.ov_rpu = nov ? ov_rpu : nullptr;
-  r.ov_unit = nov ? ov_unit : nullptr;
-  r.ov_rule = nov ? ov_rule : nullptr;
-  // the matched descriptors become an ordinary DoLimit batch in the slot's staging
-  PackOut po{h.stem, h.off, h.req, h.unit, h.flags, h.limit, h.hits, h.rule, c->cfg.max_stem_bytes};
-  launch_match(c->cfg_dev, r, m, po, M + o_tmp, scan, st);
-  HIPCHK(c, hipGetLastError());
-  // (by a kernel's stores: a DMA copy back would queue behind the next batch's input copy)
-  ToHost th{};
-  th.src[0] = M + o_cnt;
-  th.dst[0] = (uint8_t*)s.h_cnt;
-  th.bytes[0] = 16;
-  th.n = 1;
-  HIPCHK(c, copy_to_host(th, st));
-  HIPCHK(c, hipEventRecord(s.count_done, st));
-  s.n = n;
-  s.nq = nq;
-  s.n_rules = in->n_rules;
-  s.opts = opts;
-  s.seq = c->seq_sub++;
-  s.r = r;
-  s.m = m;
-  s.ro = ReqOutDev{M + o_code, (uint32_t*)(M + o_rem), (uint32_t*)(M + o_reset), M + o_match,
-                   (uint32_t*)(M + o_orule), (uint32_t*)(M + o_orpu), M + o_ounit};
-  s.vblock = verdict ? M + o_verdict : nullptr;
-  s.has_out = out != nullptr;
-  s.has_verdict = verdict != nullptr;
-  s.stage = 0;
-  s.wire = s.failed = s.has_resp = s.ov = false;
-  if (out) s.out = *out;
-  if (verdict) s.verdict = *verdict;
-  if (verdict && !nq && verdict->global_shadow) *verdict->global_shadow = 0;
-  c->rq_n++;
-  return RL_OK;
-}
-
-// ---- serialized payloads parsed on the device (rl_do_limit_wire_async) ------
-
-int eng_do_limit_wire_async(Engine* c, const rl_wire_batch* in, rl_wire_result* wire, rl_request_result* out,
-                            uint32_t opts, rl_request_verdict* verdict, const rl_response_format* fmt,
-                            rl_response_batch* resp) {
-  if (!c || !in || !wire || !wire->req_status || (!out && !verdict && !resp))
-    return set_err(c, RL_E_INVALID, "gpu: null argument");
-  rlresp::Format rf{};
-  uint8_t* resp_dst = nullptr;
-  if (resp) {
-    if (!resp->bytes || !resp->resp_off) return set_err(c, RL_E_INVALID, "gpu: rl_response_batch without bytes or resp_off");
-    if (!rlresp::format_from(fmt, &rf))
-      return set_err(c, RL_E_INVALID, "gpu: rl_response_format: key over 64 bytes, NULL key with a length or reserved not zero");
-  }
-  if (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
-  if (wire->reserved) return set_err(c, RL_E_INVALID, "gpu: rl_wire_result: reserved field not zero");
-  if (!c->cfg_loaded) return set_err(c, RL_E_INVALID, "gpu: no rate limit configuration loaded");
-  const rl_config& g = c->cfg;
-  const uint32_t nq = in->n_requests;
-  if (nq > g.max_requests || in->n_rules > g.max_rules)
-    return set_err(c, RL_E_CAPACITY, "gpu: wire batch exceeds configured max_requests/max_rules");
-  const uint64_t B = in->buf_bytes;
-  if (!in->buf) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  auto sect = [&](uint64_t off, uint64_t bytes) { return off % 4 == 0 && off <= B && bytes <= B - off; };
-  if (in->msgs_bytes > 0xFFFFFFFFull || !sect(in->msg_off, (nq + 1) * 4ull) || !sect(in->now, nq * 4ull) ||
-      !sect(in->msgs, in->msgs_bytes))
-    return set_err(c, RL_E_INVALID, "gpu: wire batch section outside buf or not 4-byte aligned");
-  // (the two ends only: every offset between them is checked on the device)
-  const uint32_t* mo = reinterpret_cast<const uint32_t*>(in->buf + in->msg_off);
-  if (mo[0] || mo[nq] != in->msgs_bytes)
-    return set_err(c, RL_E_INVALID, "gpu: wire batch msg_off does not start at zero or end at msgs_bytes");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  if (resp && resp->bytes_cap) {
-    // the responses go out by a kernel's stores: both ends inside one page-locked allocation
-    void* dp = nullptr;
-    void* de = nullptr;
-    if (hipHostGetDevicePointer(&dp, resp->bytes, 0) != hipSuccess || !dp ||
-        hipHostGetDevicePointer(&de, resp->bytes + resp->bytes_cap - 1, 0) != hipSuccess ||
-        (uint8_t*)de != (uint8_t*)dp + resp->bytes_cap - 1) {
-      (void)hipGetLastError();  // (the failed lookup's sticky error: pageable memory)
-      return set_err(c, RL_E_INVALID, "gpu: rl_response_batch.bytes is not page-locked over bytes_cap (rl_alloc_host)");
-    }
-    resp_dst = (uint8_t*)dp;
-  }
-  int rc;
-  if ((rc = ensure_request_slots(c))) return rc;
-  if ((rc = eng_requests_advance(c, c->rq_n == RL_REQUESTS_INFLIGHT ? 1 : 0))) return rc;
-  RequestSlot& s = c->rq[(c->rq_head + c->rq_n) % RL_REQUESTS_INFLIGHT];
-  HostSlot& h = s.h;
-  hipStream_t st = s.st;  // (after the slot's previous batch, in stream order)
-  if (!s.h_wcnt) {
-    HIPCHK(c, hipHostMalloc((void**)&s.h_wcnt, 32, hipHostMallocDefault));
-    HIPCHK(c, hipEventCreateWithFlags(&s.wire_done, hipEventDisableTiming));
-  }
-  const uint32_t T = (nq + RL_WIRE_TILE - 1) / RL_WIRE_TILE;
-  size_t need = 0;
-  auto piece = [&need](size_t bytes) {
-    const size_t o = need;
-    need += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_reqw = piece(nq * 16ull), o_tsum = piece(T * 16ull), o_index = piece((T + 1) * 16ull),
-               o_cnt = piece(32), o_status = piece(nq), o_first = piece((nq + 1) * 4ull),
-               o_miss = c->ov_on ? piece(nq * 4ull) : 0;
-  if (need > s.wbuf_cap || B > h.cbuf_cap) HIPCHK(c, hipStreamSynchronize(st));  // the slot's previous batch
-  if (need > s.wbuf_cap) {
-    if (s.wbuf) HIPCHK(c, hipFree(s.wbuf));
-    s.wbuf = nullptr;
-    s.wbuf_cap = 0;
-    HIPCHK(c, hipMalloc((void**)&s.wbuf, need));
-    s.wbuf_cap = need;
-  }
-  if (B > h.cbuf_cap) {
-    if (h.cbuf) HIPCHK(c, hipFree(h.cbuf));
-    h.cbuf = nullptr;
-    h.cbuf_cap = 0;
-    HIPCHK(c, dalloc(&h.cbuf, B + 64));
-    h.cbuf_cap = B;
-  }
-  if (c->seq_sub - c->seq_done >= PROGRESS_RING) {
-    HIPCHK(c, hipEventSynchronize(c->done_ring[c->seq_done % PROGRESS_RING]));
-    c->seq_done++;
-  }
-  if (B) {  // (on the copy stream, as the packed batches' buffers)
-    HIPCHK(c, hipMemcpyAsync(h.cbuf, in->buf, B, hipMemcpyHostToDevice, c->rq_copy));
-    HIPCHK(c, hipEventRecord(h.in_done, c->rq_copy));
-    HIPCHK(c, hipStreamWaitEvent(st, h.in_done, 0));
-  }
-  uint8_t* W = s.wbuf;
-  WireDev w;
-  w.n_req = nq;
-  w.tiles = T;
-  w.msgs_bytes = (uint32_t)in->msgs_bytes;
-  w.msg_off = (const uint32_t*)(h.cbuf + in->msg_off);
-  w.now32 = (const uint32_t*)(h.cbuf + in->now);
-  w.msgs = h.cbuf + in->msgs;
-  w.reqw = (uint4*)(W + o_reqw);
-  w.tsum = (uint4*)(W + o_tsum);
-  w.index = (uint4*)(W + o_index);
-  w.cnt = (uint32_t*)(W + o_cnt);
-  w.status = W + o_status;
-  w.desc_first = (uint32_t*)(W + o_first);
-  w.n_rules = in->n_rules;
-  w.miss = c->ov_on ? (uint32_t*)(W + o_miss) : nullptr;
-  HIPCHK(c, hipMemsetAsync(w.cnt, 0, 32, st));
-  launch_wire_count(w, st, c->ov_on ? &c->ov : nullptr, c->ov_order, c->ov_ordered);
-  if (c->ov_on && T) c->ov_ordered = true;
-  HIPCHK(c, hipGetLastError());
-  ToHost th{};
-  th.src[0] = (const uint8_t*)w.cnt;
-  th.dst[0] = (uint8_t*)s.h_wcnt;
-  th.bytes[0] = 32;
-  th.n = 1;
-  HIPCHK(c, copy_to_host(th, st));
-  HIPCHK(c, hipEventRecord(s.wire_done, st));
-  s.stage = 1;
-  s.wire = true;
-  s.failed = false;
-  s.ov = c->ov_on;
-  s.w = w;
-  s.wres = *wire;
-  s.n = 0;
-  s.nq = nq;
-  s.n_rules = in->n_rules;
-  s.opts = opts;
-  s.seq = c->seq_sub++;
-  s.has_out = out != nullptr;
-  s.has_verdict = verdict != nullptr;
-  if (out) s.out = *out;
-  if (verdict) s.verdict = *verdict;
-  if (verdict && !nq && verdict->global_shadow) *verdict->global_shadow = 0;
-  s.has_resp = resp != nullptr;
-  if (resp) {
-    s.fmt = rf;
-    s.resp = *resp;
-    s.resp_dst = resp_dst;
-    if (!nq) resp->resp_off[0] = 0;
-  }
-  c->rq_n++;
-  return RL_OK;
-}
-
-// ---- override stats keys interned on the device (rl_override_rules_enable) --
-
-int eng_override_rules_enable(Engine* c, const rl_override_rules_config* cfg) {
-  if (!c || !cfg) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  if (c->ov_on) return set_err(c, RL_E_INVALID, "gpu: rl_override_rules_enable: already enabled on this ctx");
-  if (cfg->reserved[0] || cfg->reserved[1] || cfg->reserved[2] || cfg->reserved[3])
-    return set_err(c, RL_E_INVALID, "gpu: rl_override_rules_config: reserved field not zero");
-  if (!cfg->capacity || (uint64_t)cfg->first_rule + cfg->capacity > c->cfg.max_rules)
-    return set_err(c, RL_E_INVALID, "gpu: rl_override_rules_config: capacity zero or first_rule + capacity > max_rules");
-  RQ_SETTLE(c);
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  // (offsets into the arena are 32-bit: it holds at most 4 GiB - 1)
-  const uint64_t want = cfg->key_bytes ? cfg->key_bytes : 64ull * cfg->capacity;
-  const uint32_t arena_cap = (uint32_t)std::min<uint64_t>(want, 0xFFFFFFFFull);
-  uint64_t nslots = 64;
-  while (nslots < 4ull * cfg->capacity) nslots *= 2;  // (a quarter full at the most: short probes)
-  OvDev t{};
-  hipEvent_t ev = nullptr;
-  const bool ok = dalloc(&t.slots, nslots) == hipSuccess && dalloc(&t.koff, cfg->capacity) == hipSuccess &&
-                  dalloc(&t.klen, cfg->capacity) == hipSuccess && dalloc(&t.arena, arena_cap) == hipSuccess &&
-                  dalloc(&t.ctr, 2) == hipSuccess &&
-                  hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess &&
-                  hipMemsetAsync(t.slots, 0, nslots * 8, c->stream) == hipSuccess &&
-                  hipMemsetAsync(t.ctr, 0, 16, c->stream) == hipSuccess &&
-                  hipStreamSynchronize(c->stream) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    for (void* p : {(void*)t.slots, (void*)t.koff, (void*)t.klen, (void*)t.arena, (void*)t.ctr})
-      if (p) (void)hipFree(p);
-    if (ev) (void)hipEventDestroy(ev);
-    return set_err(c, RL_E_HIP, "gpu: rl_override_rules_enable: device allocation failed");
-  }
-  t.mask = (uint32_t)(nslots - 1);
-  t.first_rule = cfg->first_rule;
-  t.capacity = cfg->capacity;
-  t.arena_cap = arena_cap;
-  t.k0 = c->hk.k0;
-  t.k1 = c->hk.k1;
-  c->ov = t;
-  c->ov_order = ev;
-  c->ov_on = true;
-  return RL_OK;
-}
-
-namespace {
-// The table's counter words, after every submitted batch.
-int ov_counters(Engine* c, unsigned long long* ctr) {
-  RQ_SETTLE(c);
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipStream_t st = c->stream;
-  HIPCHK(c, after_batches(c, st));
-  if (c->ov_ordered) HIPCHK(c, hipStreamWaitEvent(st, c->ov_order, 0));
-  HIPCHK(c, hipMemcpyAsync(ctr, c->ov.ctr, 16, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return RL_OK;
-}
-}  // namespace
-
-int eng_override_rules_info_get(Engine* c, rl_override_rules_info* info) {
-  if (!c || !info) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  if (!c->ov_on) return set_err(c, RL_E_INVALID, "gpu: override rules are not enabled on this ctx (rl_override_rules_enable)");
-  unsigned long long ctr[2];
-  if (const int rc = ov_counters(c, ctr)) return rc;
-  rl_override_rules_info x{};
-  x.first_rule = c->ov.first_rule;
-  x.capacity = c->ov.capacity;
-  x.rules = (uint32_t)(ctr[0] >> 32);
-  x.key_bytes_used = (uint32_t)ctr[0];
-  x.key_bytes_cap = c->ov.arena_cap;
-  x.deferred_full = ctr[1];
-  *info = x;
-  return RL_OK;
-}
-
-int eng_override_rule_keys(Engine* c, uint32_t from_rule, uint32_t n, uint8_t* bytes, uint64_t cap, uint32_t* off,
-                           uint64_t* needed) {
-  if (!c || !off) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  if (!c->ov_on) return set_err(c, RL_E_INVALID, "gpu: override rules are not enabled on this ctx (rl_override_rules_enable)");
-  unsigned long long ctr[2];
-  if (const int rc = ov_counters(c, ctr)) return rc;
-  const uint32_t rules = (uint32_t)(ctr[0] >> 32), first = c->ov.first_rule;
-  if (from_rule < first || from_rule - first > rules || n > rules - (from_rule - first))
-    return set_err(c, RL_E_INVALID, "gpu: rl_override_rule_keys: range outside the ids handed out");
-  off[0] = 0;
-  if (needed) *needed = 0;
-  if (!n) return RL_OK;
-  const uint32_t i0 = from_rule - first;
-  std::vector<uint32_t> koff(n), klen(n);
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync(koff.data(), c->ov.koff + i0, n * 4ull, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(klen.data(), c->ov.klen + i0, n * 4ull, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < n; i++) {
-    if (koff[i] > c->ov.arena_cap || klen[i] > c->ov.arena_cap - koff[i])
-      return set_err(c, RL_E_HIP, "gpu: rl_override_rule_keys: a key lies outside the arena");
-    total += klen[i];
-    off[i + 1] = (uint32_t)total;
-  }
-  if (needed) *needed = total;
-  if (total > cap || total > 0xFFFFFFFFull || (total && !bytes))
-    return set_err(c, RL_E_CAPACITY, "gpu: rl_override_rule_keys: the keys take " + std::to_string(total) + " bytes");
-  // (ids are handed out with their bytes, in one step: consecutive ids lie next to each other unless
-  // inserts raced; copied key by key all the same, the call is rare)
-  for (uint32_t i = 0; i < n; i++)
-    if (klen[i])
-      HIPCHK(c, hipMemcpyAsync(bytes + off[i], c->ov.arena + koff[i], klen[i], hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return RL_OK;
-}
-
-int eng_debug_respond(Engine* c, uint32_t nq, uint32_t n, const uint32_t* req_idx, const uint8_t* req_status,
-                      const rl_request_result* ans, uint32_t opts, const rl_response_format* fmt,
-                      rl_response_batch* resp) {
-  if (!c || !resp || !resp->resp_off || !ans) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  RQ_SETTLE(c);
-  if (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
-  rlresp::Format rf{};
-  if (!rlresp::format_from(fmt, &rf))
-    return set_err(c, RL_E_INVALID, "gpu: rl_response_format: key over 64 bytes, NULL key with a length or reserved not zero");
-  if (n > c->cfg.max_batch || nq > c->cfg.max_requests)
-    return set_err(c, RL_E_CAPACITY, "gpu: verdict input exceeds configured max_batch/max_requests");
-  if (n && (!req_idx || !ans->match || !ans->code || !ans->limit_remaining || !ans->reset_s ||
-            !ans->requests_per_unit || !ans->unit))
-    return set_err(c, RL_E_INVALID, "gpu: null answer array");
-  std::vector<uint32_t> first((size_t)nq + 1, 0);
-  for (uint32_t d = 0; d < n; d++) {
-    if (req_idx[d] >= nq || (d && req_idx[d] < req_idx[d - 1]))
-      return set_err(c, RL_E_INVALID, "gpu: req_idx must be non-decreasing and below n_requests");
-    if (req_status && req_status[req_idx[d]] != RL_WIRE_OK)
-      return set_err(c, RL_E_INVALID, "gpu: a deferred or malformed request has no descriptors");
-    if (ans->reset_s[d] >= (1u << 21)) return set_err(c, RL_E_INVALID, "gpu: reset_s must be below 2^21");
-    first[req_idx[d] + 1]++;
-  }
-  for (uint32_t q = 0; q < nq; q++) first[q + 1] += first[q];
-  resp->resp_off[0] = 0;
-  if (!nq) return RL_OK;
-  const uint64_t bound = rlresp::bound(nq, n, rf);
-  if (!resp->bytes) return set_err(c, RL_E_INVALID, "gpu: rl_response_batch without bytes or resp_off");
-  if (bound > resp->bytes_cap || bound >= (1ull << 32))
-    return set_err(c, RL_E_CAPACITY, "gpu: rl_response_bound exceeds bytes_cap or 32 bits");
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  const VerdictLayout vl = verdict_layout(nq);
-  const RespLayout rl = resp_layout(nq, n, bound);
-  size_t need = 0;
-  auto piece = [&need](size_t bytes) {
-    const size_t o = need;
-    need += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_req = piece(n * 4ull), o_first = piece((nq + 1) * 4ull), o_status = piece(nq), o_match = piece(n),
-               o_code = piece(n), o_rem = piece(n * 4ull), o_reset = piece(n * 4ull), o_rpu = piece(n * 4ull),
-               o_unit = piece(n), o_verdict = piece(vl.bytes), o_resp = piece(rl.total);
-  uint8_t* B = nullptr;
-  HIPCHK(c, hipMalloc((void**)&B, need));
-  hipStream_t st = c->stream;
-  auto run = [&]() -> hipError_t {
-    hipError_t e = after_batches(c, st);
-    auto h2d = [&](size_t off, const void* src, size_t bytes) {
-      if (e == hipSuccess && bytes) e = hipMemcpyAsync(B + off, src, bytes, hipMemcpyHostToDevice, st);
-    };
-    h2d(o_req, req_idx, n * 4ull);
-    h2d(o_first, first.data(), (nq + 1) * 4ull);
-    if (req_status) h2d(o_status, req_status, nq);
-    h2d(o_match, ans->match, n);
-    h2d(o_code, ans->code, n);
-    h2d(o_rem, ans->limit_remaining, n * 4ull);
-    h2d(o_reset, ans->reset_s, n * 4ull);
-    h2d(o_rpu, ans->requests_per_unit, n * 4ull);
-    h2d(o_unit, ans->unit, n);
-    if (e != hipSuccess) return e;
-    const ReqOutDev ro{B + o_code, (uint32_t*)(B + o_rem), (uint32_t*)(B + o_reset), B + o_match, nullptr,
-                       (uint32_t*)(B + o_rpu), B + o_unit};
-    const VerdictDev vd = verdict_view(nq, n, opts, (const uint32_t*)(B + o_req), ro.match, ro.code, ro.rem, ro.reset,
-                                       ro.rpu, B + o_verdict);
-    e = launch_verdict(vd, B + o_verdict, st);
-    if (e != hipSuccess) return e;
-    if (req_status) launch_wire_code(B + o_status, B + o_verdict + vl.o_code, nq, st);
-    const RespDev rd = resp_view(nq, n, bound, (const uint32_t*)(B + o_req), (const uint32_t*)(B + o_first),
-                                 req_status ? B + o_status : nullptr, ro, B + o_verdict, B + o_resp);
-    e = launch_respond(rd, rf, st);
-    if (e != hipSuccess) return e;
-    e = hipMemcpyAsync(resp->resp_off, rd.resp_off, (nq + 1) * 4ull, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return e;
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return e;
-    const uint64_t total = std::min<uint64_t>(resp->resp_off[nq], bound);
-    if (total) e = hipMemcpyAsync(resp->bytes, rd.bytes, total, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return e;
-    return hipStreamSynchronize(st);
-  };
-  const hipError_t e = run();
-  (void)hipFree(B);
-  HIPCHK(c, e);
-  return RL_OK;
-}
-
-int eng_debug_verdict(Engine* c, uint32_t nq, uint32_t n, const uint32_t* req_idx, const uint8_t* match,
-                      const uint8_t* code, const uint32_t* limit_remaining, const uint32_t* reset_s,
-                      const uint32_t* requests_per_unit, uint32_t opts, rl_request_verdict* verdict) {
-  if (!c || !verdict) return set_err(c, RL_E_INVALID, "gpu: null argument");
-  RQ_SETTLE(c);
-  if (nq && !verdict->overall_code) return set_err(c, RL_E_INVALID, "gpu: rl_request_verdict without overall_code");
-  if (opts & ~RL_VERDICT_OPT_GLOBAL_SHADOW) return set_err(c, RL_E_INVALID, "gpu: unknown verdict option");
-  if (n > c->cfg.max_batch || nq > c->cfg.max_requests)
-    return set_err(c, RL_E_CAPACITY, "gpu: verdict input exceeds configured max_batch/max_requests");
-  if (n && (!req_idx || !match || !code || !limit_remaining || !reset_s || !requests_per_unit))
-    return set_err(c, RL_E_INVALID, "gpu: null verdict input array");
-  for (uint32_t d = 0; d < n; d++)
-    if (req_idx[d] >= nq || (d && req_idx[d] < req_idx[d - 1]))
-      return set_err(c, RL_E_INVALID, "gpu: req_idx must be non-decreasing and below n_requests");
-  if (!nq) {
-    if (verdict->global_shadow) *verdict->global_shadow = 0;
-    return RL_OK;
-  }
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  const VerdictLayout vl = verdict_layout(nq);
-  size_t need = 0;
-  auto piece = [&need](size_t bytes) {
-    const size_t o = need;
-    need += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_req = piece(n * 4ull), o_match = piece(n), o_code = piece(n), o_rem = piece(n * 4ull),
-               o_reset = piece(n * 4ull), o_rpu = piece(n * 4ull), o_verdict = piece(vl.bytes);
-  uint8_t* B = nullptr;
-  HIPCHK(c, hipMalloc((void**)&B, need));
-  hipStream_t st = c->stream;
-  auto run = [&]() -> hipError_t {
-    hipError_t e = after_batches(c, st);
-    auto h2d = [&](size_t off, const void* src, size_t bytes) {
-      if (e == hipSuccess && bytes) e = hipMemcpyAsync(B + off, src, bytes, hipMemcpyHostToDevice, st);
-    };
-    h2d(o_req, req_idx, n * 4ull);
-    h2d(o_match, match, n);
-    h2d(o_code, code, n);
-    h2d(o_rem, limit_remaining, n * 4ull);
-    h2d(o_reset, reset_s, n * 4ull);
-    h2d(o_rpu, requests_per_unit, n * 4ull);
-    if (e != hipSuccess) return e;
-    const VerdictDev vd = verdict_view(nq, n, opts, (const uint32_t*)(B + o_req), B + o_match, B + o_code,
-                                       (const uint32_t*)(B + o_rem), (const uint32_t*)(B + o_reset),
-                                       (const uint32_t*)(B + o_rpu), B + o_verdict);
-    e = launch_verdict(vd, B + o_verdict, st);
-    if (e != hipSuccess) return e;
-    e = verdict_d2h(B + o_verdict, nq, verdict, st);
-    if (e != hipSuccess) return e;
-    return hipStreamSynchronize(st);
-  };
-  const hipError_t e = run();
-  (void)hipFree(B);
-  HIPCHK(c, e);
   return RL_OK;
 }
 
